@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the Pasero Transformer training hot path on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -17,7 +17,9 @@ all-reduce over RCCL, i.e. what `Trainer.train_step` does between `zero_grad` an
 (256, 128, 128) per GPU, dropout 0.1, label smoothing 0.1, inputs resident in HBM before the timed region.
 Metric: target tokens/s (non-pad positions of decoder_input[:, 1:], the reference's own `wps`), whole job.
 
-Rank 0 prints ONE JSON line (schema in the task contract) with two extra objects:
+A plain run sets up, warms up, times the K steps (`ms_per_step` = the wall time of one of them), writes the last step's
+outputs with --dump-outputs and prints the line.  With --full, rank 0's ONE JSON line also carries the sub-window spread
+and shader clock of the timed region, the other single-GPU workloads (`extra_workloads`) and two extra objects:
   roofline     — the dominant kernel (bf16 MFMA GEMM instantiation with the largest total time): algorithmic FLOPs per
                  launch (2*M*N*K) / average launch duration, measured with HIP events on the launch stream INSIDE the
                  timed region, against the 2.5 PFLOP/s dense bf16 MFMA peak;
@@ -61,6 +63,7 @@ IWSLT_OVERRIDES = dict(input_dim=1024, conv_input_dim=80, conv_kernel_sizes=[5],
 IWSLT_TRAIN_REGEX = r'(.*\.in_linear|.*\.subsample|encoder\.layers\.[0-2]\.|.*\.adapters|encoder\.layernorm_embedding)'
 SPEECH = ('c4_whisper', 'c4_iwslt')       # S counts input frames; the encoder layers see S / 2 positions
 DEVICE_INIT = ('c5_nllb_1b3', 'c4_iwslt')  # 1.4 G parameters: created and drawn on the device (a CPU init takes a minute)
+DUMP_BUDGET_BYTES = 48 << 20               # --dump-outputs: the gradients' share of the files
 
 
 def build_workload(workload: str, dtype, device, rank: int = 0, world: int = 1):
@@ -130,7 +133,18 @@ def parse_args():
                     help='CPU rehearsal of the multi-rank plumbing (launcher, rendezvous, reducer, fused logs '
                          'all-reduce, timing protocol, JSON): a small torch MLP stands in for the HIP model, which has '
                          'no CPU path.  The line it prints is marked "rehearsal" and is not a measurement.')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the roofline (per-launch GEMM timing in '
+                         'the timed region, live PMC traffic passes), the spread over sub-windows and the shader clock, '
+                         'the other BASELINE workloads and the CPU baseline.  Without it a run sets up, warms up, times '
+                         '--steps steps and prints the line.')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the last timed step computed (loss, logs, every parameter's gradient; a fixed "
+                         "sample of the larger gradients, %d MB at most) to DIR/<name>.npy" % (DUMP_BUDGET_BYTES >> 20))
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def self_launch(args) -> int:
@@ -395,6 +409,34 @@ def count_flops(cfg, B: int, S: int, T: int, V: int, trained_encoder_layers=None
     return (2.0 * (enc_lin + dec_lin + voc) + enc_lin * trained_encoder_layers / Le + 3.0 * (enc_att + dec_att))
 
 
+def dump_outputs(out_dir: str, loss, logs, model) -> None:
+    """what a caller of the timed step receives from its last run, as .npy files: `loss.npy` (0-d fp32), `logs.npy`
+    (fp64: loss, nll_loss, num_tokens, num_lines) and `grad.<parameter>.npy` (fp32, flattened) for every parameter with a
+    gradient.  The gradients share DUMP_BUDGET_BYTES: the small ones are written whole, each larger one as the same number
+    of its elements at sorted indices drawn from a generator seeded by the parameter's name, so that two builds' files
+    compare element for element."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'loss.npy'), loss.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, 'logs.npy'),
+            np.array([logs[k] for k in ('loss', 'nll_loss', 'num_tokens', 'num_lines')], dtype=np.float64))
+    grads = [(n, p.grad.detach().reshape(-1)) for n, p in model.named_parameters() if p.grad is not None]
+    # the largest per-tensor count `cap` with sum(min(numel, cap)) inside the budget (None: everything fits whole)
+    sizes, left, cap = sorted(g.numel() for _, g in grads), DUMP_BUDGET_BYTES // 4, None
+    for i, s in enumerate(sizes):
+        if s > left // (len(sizes) - i):
+            cap = left // (len(sizes) - i)
+            break
+        left -= s
+    for n, g in grads:
+        if cap is not None and g.numel() > cap:
+            gen = torch.Generator().manual_seed(zlib.crc32(n.encode()))
+            idx = torch.unique(torch.randint(g.numel(), (cap,), generator=gen))  # sorted, distinct
+            g = g[idx.to(g.device)]
+        np.save(os.path.join(out_dir, f'grad.{n}.npy'), g.float().cpu().numpy())
+
+
 def rehearse_cpu(args, rank: int, world: int):
     """CPU rehearsal of everything around the HIP model in a multi-rank run: rendezvous, the bucketed reducer, the
     fused logs all-reduce, the barrier / max-over-ranks timing protocol and rank 0's JSON line.  Not a measurement."""
@@ -504,11 +546,16 @@ def run(args):
             dist.barrier()
         torch.cuda.synchronize()
 
+    roofline_on = args.full and not args.no_roofline
+
     def measure(workload: str, steps: int, warmup: int, with_ddp: bool):
-        """build `workload`, run `warmup` untimed + `steps` timed steps -> (elapsed s, tokens, GemmTimer, cfg, dims, ddp)"""
+        """build `workload`, run `warmup` untimed + `steps` timed steps -> (elapsed s, tokens, GemmTimer, cfg, dims, ddp,
+        last): `last` holds what the last timed step returned (loss, logs) and the model its gradients are on.  The
+        GemmTimer's samples, sub-windows and clock are only taken with --full."""
         cfg_name, V, B, S, T = WORKLOADS[workload]
         cfg, model, batch, wav = build_workload(workload, dtype, device, rank, world)
         ddp = DistributedDataParallel(model) if with_ddp else model
+        last = {'model': model}
 
         def step():
             for p in model.parameters():
@@ -520,29 +567,35 @@ def run(args):
             loss.backward()
             if dist.is_initialized():  # Trainer.train_step's per-step log exchange (training.py:431), as ONE all-reduce
                 logs = reduce_logs(logs)
+            last['loss'], last['logs'] = loss, logs
             return logs['num_tokens']  # N > 1: already the sum over the ranks
 
         timer = GemmTimer()
+        timer.windows = timer.sclk = None
         for _ in range(warmup):
             step()
         fence()
         if not args.no_roofline:
             # the sample buffer is sized from a COUNTED step (one more untimed step with every GEMM call sampled): a fixed
             # guess of 400 launches per step filled up at 54-69 % of the timed region of C5 (586) and the IWSLT recipe (759),
-            # so their per-kernel averages and `gemm_share_of_step` came from the first part of it only
-            timer.start(4096, stride=1)
+            # so their per-kernel averages and `gemm_share_of_step` came from the first part of it only.
+            # Without --full the step runs unsampled: the timed steps draw the same dropout offsets either way
+            if roofline_on:
+                timer.start(4096, stride=1)
             step()
             fence()
-            timer.stop()
-            timer.launches_per_step = timer.samples
-            timer.start(timer.launches_per_step * steps // GemmTimer.STRIDE + 64)
+            if roofline_on:
+                timer.stop()
+                timer.launches_per_step = timer.samples
+                timer.start(timer.launches_per_step * steps // GemmTimer.STRIDE + 64)
         # five sub-windows of the timed region, cut by events on the launch stream (no synchronisation inside the region):
         # one short sample per round cannot show the 3-5 % the boxes differ by, the spread inside a run can
-        nwin = 5 if steps >= 10 else 1
-        cuts = [round(i * steps / nwin) for i in range(nwin + 1)]
+        nwin = (5 if steps >= 10 else 1) if args.full else 0
+        cuts = [round(i * steps / nwin) for i in range(nwin + 1)] if nwin else []
         marks = []
-        clock = ClockSampler(device)
-        clock.start()
+        clock = ClockSampler(device) if args.full else None
+        if clock is not None:
+            clock.start()
         t0 = time.perf_counter()
         tokens = 0
         for i in range(steps):
@@ -550,24 +603,30 @@ def run(args):
                 marks.append(torch.cuda.Event(enable_timing=True))
                 marks[-1].record()
             tokens += step()
-        marks.append(torch.cuda.Event(enable_timing=True))
-        marks[-1].record()
+        if nwin:
+            marks.append(torch.cuda.Event(enable_timing=True))
+            marks[-1].record()
         fence()
         elapsed = time.perf_counter() - t0
-        timer.sclk = clock.stop()
-        w = sorted(marks[k].elapsed_time(marks[k + 1]) / (cuts[k + 1] - cuts[k]) for k in range(nwin))
-        timer.windows = {'ms_per_step_min': w[0], 'ms_per_step_median': w[len(w) // 2], 'ms_per_step_max': w[-1],
-                         'windows': nwin, 'how': 'HIP events on the launch stream at the window boundaries'}
-        if not args.no_roofline:
+        if clock is not None:
+            timer.sclk = clock.stop()
+        if nwin:
+            w = sorted(marks[k].elapsed_time(marks[k + 1]) / (cuts[k + 1] - cuts[k]) for k in range(nwin))
+            timer.windows = {'ms_per_step_min': w[0], 'ms_per_step_median': w[len(w) // 2], 'ms_per_step_max': w[-1],
+                             'windows': nwin, 'how': 'HIP events on the launch stream at the window boundaries'}
+        if roofline_on:
             timer.stop()
         if world > 1:
             t = torch.tensor([elapsed], dtype=torch.float64, device=device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = t.item()
-        return elapsed, tokens, timer, cfg, (cfg_name, V, B, S, T), ddp
+        return elapsed, tokens, timer, cfg, (cfg_name, V, B, S, T), ddp, last
 
-    elapsed, tokens, timer, cfg, (cfg_name, V, B, S, T), ddp = measure(args.workload, args.steps, args.warmup,
-                                                                       world > 1 or args.force_ddp)
+    elapsed, tokens, timer, cfg, (cfg_name, V, B, S, T), ddp, last = measure(args.workload, args.steps, args.warmup,
+                                                                             world > 1 or args.force_ddp)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last['loss'], last['logs'], last['model'])
+    del last
 
     if rank == 0:
         # SURVEY §8d algorithmic FLOPs of one fwd+bwd batch (speech: the encoder runs on the S/2 subsampled positions;
@@ -585,8 +644,6 @@ def run(args):
             'steps': args.steps,
             'warmup': args.warmup,
             'ms_per_step': 1e3 * elapsed / args.steps,
-            'ms_per_step_windows': timer.windows,   # spread inside the timed region (rank 0)
-            'sclk_mhz': timer.sclk,                 # the shader clock held during it (rank 0)
             'higher_is_better': True,
             'scaling': 'weak',
             'vs_baseline': None,
@@ -603,9 +660,12 @@ def run(args):
                        'model_tflops_per_gpu': step_flops * args.steps / elapsed / 1e12,
                        'mfma_peak_fraction_whole_step': step_flops * args.steps / elapsed / 1e12 / PEAK_BF16_TFLOPS},
         }
-        out['config']['sclk_mhz_median'] = timer.sclk['median'] if timer.sclk else None
+        if args.full:
+            out['ms_per_step_windows'] = timer.windows  # spread inside the timed region (rank 0)
+            out['sclk_mhz'] = timer.sclk                # the shader clock held during it (rank 0)
+            out['config']['sclk_mhz_median'] = timer.sclk['median'] if timer.sclk else None
         roofline = None
-        if not args.no_roofline and timer.samples:
+        if roofline_on and timer.samples:
             summ = timer.summary()
             dom = max(summ, key=lambda k: summ[k]['total_ms'])
             d = summ[dom]
@@ -627,7 +687,7 @@ def run(args):
             if traffic:  # the same kernel against the memory roof: L2 <-> fabric bytes per launch / its duration
                 gbps = traffic / (d['avg_us'] * 1e-6) / 1e9
                 roofline['hbm'] = {'achieved': gbps, 'peak': PEAK_HBM_GBPS, 'unit': 'GB/s', 'frac': gbps / PEAK_HBM_GBPS}
-        if world == 1 and not args.no_extra_workloads and args.workload == 'c2_base_bf16':
+        if args.full and world == 1 and not args.no_extra_workloads and args.workload == 'c2_base_bf16':
             # the other BASELINE configurations that fit one GPU, timed by THIS run after the headline region (same
             # process, same protocol, a few steps each): d = 1024 is where north_star states its 40 % target
             del ddp
@@ -638,8 +698,8 @@ def run(args):
             for name in ('c3_big', 'c4_whisper', 'c5_nllb_1b3', 'c4_iwslt'):
                 torch.cuda.empty_cache()
                 e_steps = args.extra_steps if name not in DEVICE_INIT else max(1, args.extra_steps // 2)  # (80-100 ms steps)
-                e_el, e_tok, e_timer, e_cfg, (_, eV, eB, eS, eT), _m = measure(name, e_steps, 3, False)
-                del _m
+                e_el, e_tok, e_timer, e_cfg, (_, eV, eB, eS, eT), _m, _l = measure(name, e_steps, 3, False)
+                del _m, _l
                 fl = count_flops(e_cfg, eB, eS if name not in SPEECH else eS // 2, eT, eV, 3 if name == 'c4_iwslt' else None)
                 rec = {'config': f'{WORKLOADS[name][0]} V={eV}, batch (B,S,T)=({eB},{eS},{eT}), {args.dtype}',
                        'steps': e_steps, 'warmup': 3, 'ms_per_step': 1e3 * e_el / e_steps,
@@ -651,7 +711,7 @@ def run(args):
                     rec['note'] = ('examples/IWSLT2023 recipe: frozen NLLB-1.3B backbone, trainable in_linear + conv k5 + encoder '
                                    'layers 0-2 + adapters; FLOPs count forward + input gradients everywhere, weight gradients '
                                    'only where parameters train')
-                if not args.no_roofline and e_timer.samples:
+                if roofline_on and e_timer.samples:
                     es = e_timer.summary()
                     edom = max(es, key=lambda k: es[k]['total_ms'])
                     top = sorted(es, key=lambda k: -es[k]['total_ms'])[:4]  # (the full tables: profiles/rNN_<workload>_*)
@@ -670,7 +730,7 @@ def run(args):
                 out['config'][name + '_mfma_frac_whole_step'] = frac
         if roofline is not None:  # (after the extras: the line's longest table last but one)
             out['roofline'] = roofline
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args.cpu_seconds)
         _JSON_LINE.append(json.dumps(out))
     if dist.is_initialized():

@@ -54,3 +54,30 @@ def test_bench_single_rank_is_not_relaunched():
 def test_bench_under_an_external_launcher_checks_the_world_size():
     r = _run('--gpus', '2', env={'WORLD_SIZE': '1', 'RANK': '0'})
     assert r.returncode != 0 and 'WORLD_SIZE=1' in (r.stderr + r.stdout)
+
+
+def test_dump_outputs_sample_is_fixed_and_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: loss (fp32), logs (fp64) and every gradient (fp32); the small gradients whole, the large ones as a
+    fixed sample, the files inside the budget and identical from call to call"""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 1 << 20)
+    net = torch.nn.Sequential(torch.nn.Linear(512, 1024), torch.nn.Linear(1024, 64)).to(torch.bfloat16)
+    for p in net.parameters():
+        p.grad = torch.randn_like(p)
+    logs = {'loss': 1.5, 'nll_loss': 1.25, 'num_tokens': 96, 'num_lines': 4}
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(3.0), logs, net)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == sorted(os.listdir(tmp_path / 'b')) and len(files) == 2 + 4
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= (1 << 20) + 128 * len(files)
+    for f in files:
+        x, y = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    assert np.load(tmp_path / 'a' / 'logs.npy').tolist() == [1.5, 1.25, 96, 4]
+    bias = np.load(tmp_path / 'a' / 'grad.0.bias.npy')
+    assert np.array_equal(bias, net[0].bias.grad.float().numpy())  # small: whole
+    w = np.load(tmp_path / 'a' / 'grad.0.weight.npy')
+    assert 0 < w.size < net[0].weight.numel()  # large: a sample
+    assert np.isin(w, net[0].weight.grad.float().numpy().reshape(-1)).all()

@@ -4,8 +4,6 @@ rank and PASERO_DDP_FORCE_REDUCE keeps the bucket -> all-reduce(AVG) -> communic
 path live; with one rank the reduced gradients must equal the plain ones (every reduction of the step is a fixed-order
 sum: bitwise).  (The world_size-2 semantics are
 covered on CPU with gloo in test_ddp_cpu.py.)"""
-import os
-import socket
 
 import pytest
 import torch
@@ -15,12 +13,6 @@ from conftest import load_golden
 from model_utils import build_model, text_batch
 
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(('127.0.0.1', 0))
-        return s.getsockname()[1]
 
 
 def _base_width_model(dtype):
@@ -47,11 +39,10 @@ def test_rccl_bucketed_all_reduce_single_rank(monkeypatch, dtype):
     if per_op:  # the layers dispatched op by op from Python (the native layer call switched off)
         dtype = 'base_width_bf16'
         monkeypatch.setattr(native_layer, '_OFF', True)
-    monkeypatch.setenv('MASTER_ADDR', '127.0.0.1')
-    monkeypatch.setenv('MASTER_PORT', str(_free_port()))
     monkeypatch.setenv('PASERO_DDP_FORCE_REDUCE', '1')
     dev = torch.device('cuda', 0)
-    dist.init_process_group('nccl', rank=0, world_size=1, device_id=dev)
+    # one rank: an in-process store, no TCP port to race other processes of the machine for
+    dist.init_process_group('nccl', store=dist.HashStore(), rank=0, world_size=1, device_id=dev)
     try:
         if dtype == 'base_width_bf16':
             dtype = torch.bfloat16
@@ -129,11 +120,9 @@ def test_two_forwards_back_propagated_together_under_the_reducer(monkeypatch):
     by every forward and let both write the same slice)."""
     from pasero_amd import rng
     from pasero_amd.ddp import DistributedDataParallel
-    monkeypatch.setenv('MASTER_ADDR', '127.0.0.1')
-    monkeypatch.setenv('MASTER_PORT', str(_free_port()))
     monkeypatch.setenv('PASERO_DDP_FORCE_REDUCE', '1')
     dev = torch.device('cuda', 0)
-    dist.init_process_group('nccl', rank=0, world_size=1, device_id=dev)
+    dist.init_process_group('nccl', store=dist.HashStore(), rank=0, world_size=1, device_id=dev)
     try:
         model, b1 = _base_width_model(torch.bfloat16)
         b2 = {k: (v.flip(0) if v.dim() else v) for k, v in b1.items()}   # another batch: the sentences in reverse order
@@ -174,11 +163,9 @@ def test_c2_step_under_every_all_reduce_schedule_is_bitwise_the_plain_step(monke
     8-GPU node then adds is bandwidth, not arithmetic."""
     from pasero_amd import rng
     from pasero_amd.ddp import DistributedDataParallel
-    monkeypatch.setenv('MASTER_ADDR', '127.0.0.1')
-    monkeypatch.setenv('MASTER_PORT', str(_free_port()))
     monkeypatch.setenv('PASERO_DDP_FORCE_REDUCE', '1')
     dev = torch.device('cuda', 0)
-    dist.init_process_group('nccl', rank=0, world_size=1, device_id=dev)
+    dist.init_process_group('nccl', store=dist.HashStore(), rank=0, world_size=1, device_id=dev)
     try:
         model, batch = _base_width_model(torch.bfloat16)
         model.train()
@@ -204,14 +191,13 @@ def test_c2_step_under_every_all_reduce_schedule_is_bitwise_the_plain_step(monke
 # ------------------------------------------------------------------------------------------------------------
 # two ranks, the real HIP model: both processes share the box's one card (gloo carries the CUDA buckets)
 # ------------------------------------------------------------------------------------------------------------
-def _two_rank_worker(rank, world, port, ret, base_width=False):
+def _two_rank_worker(rank, world, store_file, ret, base_width=False):
     import sys
     from conftest import ROOT
     sys.path.insert(0, ROOT)
-    os.environ['MASTER_ADDR'] = '127.0.0.1'
-    os.environ['MASTER_PORT'] = str(port)
     torch.cuda.set_device(0)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
+    # rendezvous through a file of the test's own: no TCP port to race other processes of the machine for
+    dist.init_process_group('gloo', store=dist.FileStore(store_file, world), rank=rank, world_size=world)
     try:
         from pasero_amd import rng
         from pasero_amd.ddp import DistributedDataParallel
@@ -264,18 +250,18 @@ def _two_rank_worker(rank, world, port, ret, base_width=False):
 
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize('base_width', [False, True])
-def test_two_ranks_average_the_gradients_of_the_hip_model(base_width):
+def test_two_ranks_average_the_gradients_of_the_hip_model(tmp_path, base_width):
     """world_size 2 with the real model: rank r trains on its share of the batch, the bucketed reducer leaves on every
     rank (sum of the per-rank gradients) / 2 = (full-batch gradient) / 2, and the per-rank losses add up to the
     full-batch loss (fp32: 2e-4 relative, summation order only).  base_width: the bf16 base model, whose natively run
     layers write their gradients straight into their bucket slices on both ranks (bf16 round-off: 3e-2 of the largest
     entry, loss 2e-3)"""
     import torch.multiprocessing as mp
-    world, port = 2, _free_port()
+    world, store_file = 2, str(tmp_path / 'store')
     mgr = mp.Manager()
     ret = mgr.dict()
     ctx = mp.get_context('spawn')
-    procs = [ctx.Process(target=_two_rank_worker, args=(r, world, port, ret, base_width)) for r in range(world)]
+    procs = [ctx.Process(target=_two_rank_worker, args=(r, world, store_file, ret, base_width)) for r in range(world)]
     for p in procs:
         p.start()
     for p in procs:
@@ -297,10 +283,8 @@ def test_native_comm_schedules_single_rank(monkeypatch):
     multiple of the chunk the kernels use; the multi-rank equivalence with dist.all_reduce is what `RcclComm` itself
     checks at construction on whatever set of GPUs it runs on."""
     from pasero_amd.ddp import RcclComm
-    monkeypatch.setenv('MASTER_ADDR', '127.0.0.1')
-    monkeypatch.setenv('MASTER_PORT', str(_free_port()))
     dev = torch.device('cuda', 0)
-    dist.init_process_group('nccl', rank=0, world_size=1, device_id=dev)
+    dist.init_process_group('nccl', store=dist.HashStore(), rank=0, world_size=1, device_id=dev)
     try:
         comm = RcclComm.get(None, dev)
         assert comm is not None, RcclComm._instance.report
