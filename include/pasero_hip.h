@@ -414,6 +414,41 @@ int pk_decoder_step(const PkDecoderPlan* plan, const long long* ids, int B, int 
 int pk_argmax_rows(const void* x, long long rows, long long n, long long ld, long long* out, long long out_stride,
                    int dtype, void* stream);
 
+/* ---- Beam search (csrc/beam.hip): the selection of one search step and the re-ordering of the native step's caches.
+ * pk_beam_select replaces, per step of beam_search (pasero/decoding.py:1225-1657): `.float().log_softmax(-1)`, the
+ * blacklist, the forced prompt tokens, `scores += hyp_scores`, `topk(2K)` over (B, K*V), the EOS mask and
+ * `topk(beam_range + eos_mask * 2K, largest=False)` (:1391-1449, :1539-1549).  The logits are read once, in their dtype.
+ *   logits [B*K][ld]  fp32 / bf16 / fp16, ld >= V (16-byte loads when every row starts on a 16-byte boundary)
+ *   hyp_in [B*K]      scores of the live hypotheses, or NULL on the first step: then only row b*K of every sentence
+ *                     takes part (`scores[::beam_size]`)
+ *   row_bias [B*K]    or NULL: added to every score of the row (the summed prompt scores of the first call)
+ *   forced [B*K]      or NULL: a row whose forced token is neither `pad` nor `eos` keeps only that token finite
+ *   blacklist [n]     token ids whose score is -inf
+ *   eos_counts [B]    or NULL (= all 1): 0 where an EOS does not finish a hypothesis (step < prompt length)
+ *   score = ((x - max_row) - log(sum exp(x - max_row))) + row_bias + hyp_in, fp32.  Per sentence the 2K best of the K*V
+ *   scores in descending order; among equal scores the lower flat index k*V + v first (a stable descending sort).
+ *   eos flag = token == eos && isfinite(score) && eos_counts[b].
+ *   cand_score/cand_beam/cand_tok/cand_eos [B][2K]  the candidates (local beam k, token, flag); when fewer than 2K scores
+ *                     are finite the remaining slots carry -inf and a valid index
+ *   n_eos [B]         flagged candidates among the first K
+ *   sel_beam/sel_tok/sel_score [B*K]  the first K unflagged candidates in order: global row b*K + k, token, score
+ *   lse_out [B*K]     or NULL: log-sum-exp of every row that took part
+ * 1 <= K <= 16; V <= 2^27; B*K <= 65535.  NaN logits are undefined, as in the reference.  `scratch` (device, 256-byte
+ * aligned) holds pk_beam_select_scratch(B, K, V) bytes.  Two launches on `stream`, no host synchronisation.
+ * pk_beam_reorder replaces Decoder.reorder_state (pasero/models/transformer.py:68-75) for the native step's self-attention
+ * caches: dst[l][r][0:t] = src[l][sel_beam[r]][0:t] for every layer's K and V cache ([rows][cap][d]) in one launch (up to
+ * 48 layers; more are split).  The four tables are host arrays of n_layers device pointers; src and dst must be different
+ * buffers (an in-place gather races); rows >= t of dst are not written; an index outside [0, rows_in) copies nothing. */
+size_t pk_beam_select_scratch(int B, int K, long long V);
+int pk_beam_select(const void* logits, long long ld, long long V, int B, int K, int dtype, const float* hyp_in,
+                   const float* row_bias, const long long* forced, long long pad, long long eos,
+                   const long long* blacklist, int n_blacklist, const unsigned char* eos_counts, void* scratch,
+                   size_t scratch_bytes, float* cand_score, int* cand_beam, int* cand_tok, int* cand_eos, int* n_eos,
+                   long long* sel_beam, long long* sel_tok, float* sel_score, float* lse_out, void* stream);
+int pk_beam_reorder(const void* const* src_k, const void* const* src_v, void* const* dst_k, void* const* dst_v,
+                    int n_layers, const long long* sel_beam, int rows_out, int rows_in, int t, long long cap, int d,
+                    int dtype, void* stream);
+
 /* ---- "Next" row: feature collate.  Replaces the CPU pad_sequence + dtype cast of
  * utils.tokens_as_tensor for floating-point feature sequences (pasero/utils.py:709-736) as used on speech batches read
  * from NumpyFile rows (pasero/files.py:103-175): the ragged rows are uploaded once, concatenated, in the file's dtype

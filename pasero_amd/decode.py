@@ -21,7 +21,7 @@ from torch import Tensor
 
 from . import functional as F
 from . import lib
-from .lib import ACT, check, dtype_code, ptr, stream_ptr
+from .lib import ACT, check, dtype_code, ptr, require_gpu, stream_ptr
 
 _P = ctypes.c_void_p
 _LAYER_FIELDS = ['qkv_w', 'qkv_b', 'out_w', 'out_b', 'ln1_g', 'ln1_b', 'cq_w', 'cq_b', 'cout_w', 'cout_b', 'ln2_g',
@@ -192,8 +192,8 @@ class DecodeCache:
         """the reference's view of the caches: (B, t, H, hd) tensors per layer"""
         B, t, H = self.B, self.t, self.H
         for (kn, vn), ck, cv in zip(self.names, self.k, self.v):
-            state[kn] = ck[:, :t].view(B, t, H, 64)
-            state[vn] = cv[:, :t].view(B, t, H, 64)
+            state[kn] = ck[:B, :t].view(B, t, H, 64)  # (a buffer of `reorder_beam` may hold more rows than B)
+            state[vn] = cv[:B, :t].view(B, t, H, 64)
 
     def matches(self, state: dict, encoder_out: Tensor) -> bool:
         """still the caches of THIS state (nobody replaced the tensors behind our back)"""
@@ -206,8 +206,9 @@ class DecodeCache:
         for lst in (self.k, self.v):
             for i, old in enumerate(lst):
                 new = torch.empty(self.B, self.cap, self.D, device=old.device, dtype=old.dtype)
-                new[:, :self.t].copy_(old[:, :self.t])
+                new[:, :self.t].copy_(old[:self.B, :self.t])
                 lst[i] = new
+        self._spare = None
         self._tables()
 
     def step(self, ids: Tensor, pos_start: int, state: dict) -> Tensor:
@@ -226,9 +227,10 @@ class DecodeCache:
     def reorder(self, indices: Tensor, state: dict):
         """beam search (transformer.py:68-75): select sentences / hypotheses along the batch dimension"""
         idx = indices.to(self.k[0].device)
+        self.k = [c[:self.B].index_select(0, idx) for c in self.k]
+        self.v = [c[:self.B].index_select(0, idx) for c in self.v]
         self.B = idx.numel()
-        self.k = [c.index_select(0, idx) for c in self.k]
-        self.v = [c.index_select(0, idx) for c in self.v]
+        self._spare = None
         self.cross = [c.view(-1, self.S, 2 * self.D).index_select(0, idx).view(-1, 2 * self.D) for c in self.cross]
         self.mask = None if self.mask is None else self.mask.index_select(0, idx)
         nbytes = lib.load().pk_decoder_step_scratch(ctypes.byref(self.plan.c_plan), self.B)
@@ -236,6 +238,46 @@ class DecodeCache:
             self.scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.scratch.device)
         self._tables()
         self._publish(state)
+
+    _spare = None  # the second buffer set of `reorder_beam`: (k list, v list), allocated at the first beam re-ordering
+
+    def reorder_beam(self, indices: Tensor, state: dict, shrink: bool):
+        """`reorder` for `beam_search`: the same published state, less traffic.  The self-attention caches are gathered
+        by ONE pk_beam_reorder launch (rows < t only) into a second buffer set and the two sets swap (an in-place
+        gather races); the cross-attention K|V and the mask are left alone unless sentences leave the batch
+        (`shrink`) — the rows of one sentence's beams are equal, so selecting among them changes nothing."""
+        idx = indices.to(self.k[0].device).contiguous()
+        rows_in, rows_out, n = self.B, idx.numel(), len(self.names)
+        if self._spare is None:
+            self._spare = ([torch.empty_like(c) for c in self.k], [torch.empty_like(c) for c in self.v])
+        k2, v2 = self._spare
+        assert rows_out <= k2[0].size(0)
+        dk = (_P * n)(*[t.data_ptr() for t in k2])
+        dv = (_P * n)(*[t.data_ptr() for t in v2])
+        check(lib.load().pk_beam_reorder(self.k_tab, self.v_tab, dk, dv, n, ptr(idx), rows_out, rows_in, self.t, self.cap,
+                                         self.D, dtype_code(self.k[0]), stream_ptr()), 'pk_beam_reorder')
+        self._spare, self.k, self.v = (self.k, self.v), k2, v2
+        self.B = rows_out
+        if shrink:
+            self.cross = [c.view(-1, self.S, 2 * self.D).index_select(0, idx).view(-1, 2 * self.D) for c in self.cross]
+            self.mask = None if self.mask is None else self.mask.index_select(0, idx)
+        self._tables()
+        self._publish(state)
+
+    def clone(self, state: dict) -> dict:
+        """an independent copy of this cache and of the `state` dict it rides in (tests compare two re-orderings)"""
+        import copy
+        other = copy.copy(self)
+        other.k, other.v = [c.clone() for c in self.k], [c.clone() for c in self.v]
+        other.cross = [c.clone() for c in self.cross]
+        other.mask = None if self.mask is None else self.mask.clone()
+        other.scratch = torch.empty_like(self.scratch)
+        other._spare = None
+        other._tables()
+        new_state = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in state.items()}
+        new_state[DecodeCache.KEY] = other
+        other._publish(new_state)
+        return new_state
 
 
 def try_step(decoder, encoder_out: Tensor, encoder_mask: Optional[Tensor], decoder_input: Tensor, state: Optional[dict],
@@ -277,3 +319,232 @@ def try_step(decoder, encoder_out: Tensor, encoder_mask: Optional[Tensor], decod
     logits = cache.step(decoder_input, pos.shift + offset, state)
     state['offset'] = offset + 1
     return logits
+
+
+# ---- beam search (pasero/decoding.py:1225-1657) ----------------------------------------------------------------------
+class BeamSelect:
+    """buffers of pk_beam_select for searches of up to B sentences x K beams over V tokens, and the call itself.
+    After `run`: `sel_beam` / `sel_tok` (int64) and `sel_score` (fp32) hold rows [0, B*K) of the continued beams;
+    `records()` brings n_eos and the 2K candidates of every sentence to the host in ONE copy."""
+
+    def __init__(self, B: int, K: int, V: int, device):
+        L = lib.load()
+        self.B, self.K, self.V, self.R = B, K, V, 2 * K
+        # K outside [1, 16] is refused by the library (pk_beam_select); size the buffers for any K so that it gets to say so
+        self.scratch = torch.empty(max(256, L.pk_beam_select_scratch(B, K, V)), dtype=torch.uint8, device=device)
+        n = B * self.R
+        self.rec = torch.zeros(B + 4 * n, dtype=torch.int32, device=device)  # n_eos | score bits | beam | token | eos flag
+        self.n_eos = self.rec[:B]
+        self.cand_score = self.rec[B:B + n].view(torch.float32)
+        self.cand_beam, self.cand_tok, self.cand_eos = (self.rec[B + i * n:B + (i + 1) * n] for i in (1, 2, 3))
+        self.sel_beam = torch.zeros(B * K, dtype=torch.int64, device=device)
+        self.sel_tok = torch.zeros(B * K, dtype=torch.int64, device=device)
+        self._scores = [torch.zeros(B * K, dtype=torch.float32, device=device) for _ in range(2)]  # hyp_in of the next step
+        self.sel_score = self._scores[0]
+        self.lse = torch.zeros(B * K, dtype=torch.float32, device=device)
+
+    def run(self, logits: Tensor, B: int, eos: int, pad: int, hyp: Optional[Tensor] = None, row_bias: Optional[Tensor] = None,
+            forced: Optional[Tensor] = None, blacklist: Optional[Tensor] = None, eos_counts: Optional[Tensor] = None):
+        """logits (B*K, V), any row stride, fp32 / bf16 / fp16"""
+        require_gpu(logits)
+        assert logits.dim() == 2 and logits.size(0) == B * self.K and logits.size(1) == self.V and B <= self.B
+        if logits.stride(1) != 1:
+            logits = logits.contiguous()
+        ld = logits.stride(0) if logits.size(0) > 1 else max(self.V, logits.stride(0))
+        out = self._scores[1] if (hyp is not None and hyp.data_ptr() == self._scores[0].data_ptr()) else self._scores[0]
+        for t, dt in ((hyp, torch.float32), (row_bias, torch.float32), (forced, torch.int64), (blacklist, torch.int64),
+                      (eos_counts, torch.uint8)):
+            assert t is None or (t.dtype == dt and t.is_contiguous() and t.is_cuda)
+        check(lib.load().pk_beam_select(
+            ptr(logits), ld, self.V, B, self.K, dtype_code(logits), ptr(hyp), ptr(row_bias), ptr(forced), int(pad), int(eos),
+            ptr(blacklist), 0 if blacklist is None else blacklist.numel(), ptr(eos_counts), ptr(self.scratch),
+            self.scratch.numel(), ptr(self.cand_score), ptr(self.cand_beam), ptr(self.cand_tok), ptr(self.cand_eos),
+            ptr(self.n_eos), ptr(self.sel_beam), ptr(self.sel_tok), ptr(out), ptr(self.lse), stream_ptr()), 'pk_beam_select')
+        self.sel_score = out
+
+    def records(self, B: int):
+        """host copies (numpy): n_eos (B,), score / beam / token / eos flag (B, 2K) — the step's one device->host read"""
+        host = self.rec.cpu().numpy()
+        n, R = self.B * self.R, self.R
+        part = [host[self.B + i * n:self.B + i * n + B * R].reshape(B, R) for i in range(4)]
+        return host[:B], part[0].view('float32'), part[1], part[2], part[3]
+
+
+_warned_repeat_penalty = False
+
+
+def _uncollate(hyp: dict, padding_idx: int, src_mask: Optional[Tensor]):
+    """decoding.py:1660-1705 for the keys a search produces: cut what belongs to padding tokens"""
+    tokens = hyp['tokens']
+    pad_at = tokens == padding_idx
+    hyp['tokens'] = tokens[:int((~pad_at).sum())]
+    for k, v in list(hyp.items()):
+        if v is None:
+            continue
+        if k.startswith('enc_'):
+            v = v[~src_mask]
+            if k.endswith('_self_attn'):
+                v = v[..., ~src_mask]
+            hyp[k] = v
+        elif k == 'pos_scores':
+            hyp[k] = v[~pad_at]
+
+
+def beam_search(decoder, encoder_outputs, encoder_masks, max_output_len: int, beam_size: int, meta: dict, *,
+                return_scores: bool = False, decoder_input: Optional[Tensor] = None, return_layers=[],
+                sharded: bool = False, enc_layer_outputs: dict = {}, device=None, len_penalty: float = 1.0,
+                blacklist=[], **kwargs):
+    """Drop-in for pasero.decoding.beam_search (decoding.py:1225-1657): same keyword signature, same return value — a list
+    of B n-best lists of dicts ('tokens', 'score', 'normalized_score', 'pos_scores' under `return_scores`), sorted by
+    normalized score.  The decoder call is the reference's (`decoder(encoder_out, encoder_mask, tokens, state=state)`: the
+    native decoding step when a plan exists, the per-op path otherwise); what surrounds it runs on the device:
+      * one pk_beam_select call per step does log-softmax, blacklist, forced prompt tokens, + hypothesis scores, top 2K,
+        EOS mask and the choice of the K continued beams, reading the logits once in their own dtype;
+      * the native step's self-attention caches are re-ordered by one pk_beam_reorder launch (`DecodeCache.reorder_beam`);
+        the cross-attention K|V, the encoder output and its mask are only touched when a sentence leaves the batch;
+      * one device->host read per step (n_eos and the candidates); the finished-hypothesis bookkeeping is host Python.
+    Among equal scores the candidate with the lower flat index k*V + v comes first (torch.topk leaves it open).
+    Not implemented (raise, naming the option): ensembles, `return_layers`, `sharded`, decoder-only models."""
+    global _warned_repeat_penalty
+    import warnings
+    from .transformer import Decoder
+    if kwargs.get('repeat_penalty', 1.0) != 1.0 and not _warned_repeat_penalty:
+        _warned_repeat_penalty = True
+        warnings.warn("'repeat_penalty' is not supported in beam search")
+    if isinstance(encoder_outputs, (list, tuple)):
+        if len(encoder_outputs) > 1:
+            raise NotImplementedError('pasero_amd beam_search: ensembles (several decoders) are not implemented')
+        encoder_outputs = encoder_outputs[0] if encoder_outputs else None
+    if isinstance(encoder_masks, (list, tuple)):
+        encoder_masks = encoder_masks[0] if encoder_masks else None
+    if len(getattr(decoder, 'decoders', ())) > 1:
+        raise NotImplementedError('pasero_amd beam_search: ensembles (several decoders) are not implemented')
+    if return_layers:
+        raise NotImplementedError('pasero_amd beam_search: return_layers is not implemented')
+    if sharded:
+        raise NotImplementedError('pasero_amd beam_search: sharded=True is not implemented')
+    if encoder_outputs is None:
+        raise NotImplementedError('pasero_amd beam_search: decoder-only models (empty encoder_outputs) are not implemented')
+    for d in getattr(decoder, 'decoders', ()):
+        decoder = d
+    decoder.eval()
+    K = int(beam_size)
+    dev = torch.device(device) if device is not None else encoder_outputs.device
+    enc, enc_mask = encoder_outputs.to(dev), None if encoder_masks is None else encoder_masks.to(dev)
+    require_gpu(enc)
+    B0 = enc.size(0)
+    pad, eos = decoder.padding_idx, decoder.eos_idx
+    if decoder_input is None:
+        decoder_input = torch.full((B0, 1), decoder.bos_idx, dtype=torch.long, device=dev)
+    decoder_input = decoder_input.to(dev)
+    assert decoder_input.dim() == 2 and decoder_input.size(0) == B0
+    not_pad = decoder_input != pad
+    plen = (not_pad * torch.arange(1, decoder_input.size(1) + 1, device=dev)).amax(dim=1)  # utils.mask_to_len
+    lo, hi = (int(x) for x in torch.stack([plen.min(), plen.max()]).tolist())
+    assert lo > 0
+    max_len = min(decoder.max_len, hi + max_output_len)
+    assert max_len >= 1
+    tokens = torch.full((B0 * K, max_len), eos, dtype=torch.long, device=dev)  # EOS as filler: a hypothesis ends with it
+    width = min(decoder_input.size(1), max_len)
+    tokens[:, :width] = decoder_input.repeat_interleave(K, dim=0)[:, :width]
+    feed = tokens[:, :lo]
+    src_mask = enc_mask
+    enc = enc.repeat_interleave(K, dim=0)
+    enc_mask = None if enc_mask is None else enc_mask.repeat_interleave(K, dim=0)
+    cum = torch.zeros(B0 * K, max_len, dtype=torch.float32, device=dev) if return_scores else None
+    black = torch.tensor(list(blacklist), dtype=torch.int64, device=dev) if len(blacklist) else None
+    select = None
+    finished = [[] for _ in range(B0)]
+    alive = list(range(B0))      # current batch index -> initial batch index
+    plen_alive = plen
+    hyp, state, nB = None, {}, B0
+    with torch.no_grad():
+        for step in range(lo, max_len):
+            logits, _ = decoder(enc, enc_mask, feed, state=state, meta=meta)
+            if select is None:
+                select = BeamSelect(B0, K, logits.size(-1), dev)
+            bias = prompt_scores = None
+            if logits.size(1) > 1:  # the first call carries the prompt: score its tokens (decoding.py:1395-1402)
+                assert step == lo
+                nxt = feed[:, 1:]
+                prompt_scores = logits[:, :-1].float().log_softmax(dim=-1).gather(2, nxt.unsqueeze(2)).squeeze(2)
+                prompt_scores = prompt_scores * (nxt != pad)
+                bias = prompt_scores.sum(dim=1).contiguous()
+            forced = tokens[:, step].contiguous() if step < hi else None
+            counts = (plen_alive <= step).to(torch.uint8) if step < hi else None  # an EOS inside a prompt is no end
+            select.run(logits[:, -1], nB, eos, pad, hyp=hyp, row_bias=bias, forced=forced, blacklist=black, eos_counts=counts)
+            n_eos, c_score, c_beam, c_tok, c_eos = select.records(nB)
+            keep = None
+            if n_eos.any():
+                ends = [(b, j) for b in range(nB) for j in range(K) if c_eos[b, j]]
+                rows = torch.tensor([b * K + int(c_beam[b, j]) for b, j in ends], dtype=torch.long, device=dev)
+                scores = torch.tensor([float(c_score[b, j]) for b, j in ends], dtype=torch.float32, device=dev)
+                sents = tokens.index_select(0, rows)[:, 1:step + 1]
+                if return_scores:
+                    pos = cum.index_select(0, rows)[:, :step]
+                    pos[:, step - 1] = scores
+                    pos[:, 1:] = pos[:, 1:] - pos[:, :-1]  # cumulative -> per position
+                gone = []
+                for i, (b, j) in enumerate(ends):
+                    hyps = finished[alive[b]]
+                    if len(hyps) >= K:
+                        continue
+                    h = {'tokens': sents[i], 'score': -scores[i]}
+                    if return_scores:
+                        h['pos_scores'] = -pos[i]
+                    hyps.append(h)
+                    if len(hyps) == K:
+                        gone.append(b)
+                if all(len(h) >= K for h in finished):
+                    break
+                if gone:
+                    keep = [b for b in range(nB) if b not in gone]
+            idx, new_tok, hyp = select.sel_beam[:nB * K], select.sel_tok[:nB * K], select.sel_score[:nB * K]
+            if keep is not None:  # sentences with K finished hypotheses leave the batch
+                keep_t = torch.tensor(keep, dtype=torch.long, device=dev)
+                idx, new_tok, hyp = (x.view(nB, K).index_select(0, keep_t).reshape(-1) for x in (idx, new_tok, hyp))
+                hyp = hyp.contiguous()
+                alive = [alive[b] for b in keep]
+                plen_alive = plen_alive.index_select(0, keep_t)
+                nB = len(keep)
+            # `idx` addresses rows of the batch as the decoder just saw it: one gather re-orders and shrinks
+            tokens = tokens.index_select(0, idx)
+            tokens[:, step] = new_tok
+            if return_scores:
+                cum = cum.index_select(0, idx)
+                if prompt_scores is not None:
+                    cum[:, :step - 1] = prompt_scores.cumsum(dim=1).index_select(0, idx)
+                cum[:, step - 1] = hyp
+            feed = new_tok.unsqueeze(1)
+            if keep is not None:  # rows of one sentence are equal: without a departure there is nothing to move
+                enc = enc.index_select(0, idx)
+                enc_mask = None if enc_mask is None else enc_mask.index_select(0, idx)
+            cache = state.get(DecodeCache.KEY)
+            if cache is None:
+                Decoder.reorder_state(state, idx)
+            else:
+                cache.reorder_beam(idx, state, keep is not None)
+                own = {n for pair in cache.names for n in pair}
+                for k, v in state.items():
+                    if k not in own and torch.is_tensor(v) and v.dim() > 0:
+                        state[k] = v.index_select(0, idx)
+        state = None
+        if return_scores:
+            cum[:, 1:] = cum[:, 1:] - cum[:, :-1]
+            cum = -cum
+        output = []
+        for b0, nbest in enumerate(finished):
+            if not nbest:  # the length limit came before an EOS: the first live beam
+                i = alive.index(b0)
+                h = {'tokens': tokens.view(nB, K, -1)[i, 0, 1:], 'score': -hyp.view(nB, K)[i, 0]}
+                if return_scores:
+                    h['pos_scores'] = cum.view(nB, K, -1)[i, 0, :-1]
+                nbest = [h]
+            extra = {k: v[b0] for k, v in enc_layer_outputs.items() if torch.is_tensor(v)}
+            nbest = [{**h, **extra, 'normalized_score': h['score'] / (len(h['tokens']) + 1) ** len_penalty} for h in nbest]
+            nbest.sort(key=lambda h: h['normalized_score'])
+            output.append(nbest)
+        for b0, nbest in enumerate(output):
+            for h in nbest:
+                _uncollate(h, pad, None if src_mask is None else src_mask[b0])
+    return output

@@ -42,6 +42,9 @@ SIGNATURES = {
     'pk_decoder_step_scratch': (SZ, [P, I]),
     'pk_decoder_step': (I, [P, P, I, I, I, P, P, LL, P, P, I, P, SZ, P, LL, P]),
     'pk_argmax_rows': (I, [P, LL, LL, LL, P, LL, I, P]),
+    'pk_beam_select_scratch': (SZ, [I, I, LL]),
+    'pk_beam_select': (I, [P, LL, LL, I, I, I, P, P, P, LL, LL, P, I, P, P, SZ, P, P, P, P, P, P, P, P, P, P]),
+    'pk_beam_reorder': (I, [P, P, P, P, I, P, I, I, I, LL, I, I, P]),
     'pk_pad_rows': (I, [P, I, P, P, I, I, LL, I, P]),
     'pk_residual_ln_fwd': (I, [P, P, P, P, P, P, P, P, LL, I, F, F, ULL, ULL, I, P]),
     'pk_residual_ln_bwd_workspace': (SZ, [LL, I]),
