@@ -18,6 +18,8 @@
  *     the same (seed, offset) as the forward call and regenerates the mask, nothing is stored.  Element i is kept iff
  *     the 16-bit draw number (i & 7) of philox(seed, offset, i >> 3) is >= floor(p * 65536): one evaluation serves the
  *     eight elements of a 16-byte chunk (p is quantised to 1/65536; the kept values are scaled by 1 / (1 - p)).
+ *   - sampling draws (pk_sample_select) come from the same function: row r's uniform is the top 24 bits of word 0 of
+ *     philox(seed, offset, r), times 2^-24 — in [0, 1), one (seed, offset) per decoding step.
  */
 #ifndef PASERO_HIP_H
 #define PASERO_HIP_H
@@ -448,6 +450,40 @@ int pk_beam_select(const void* logits, long long ld, long long V, int B, int K, 
 int pk_beam_reorder(const void* const* src_k, const void* const* src_v, void* const* dst_k, void* const* dst_v,
                     int n_layers, const long long* sel_beam, int rows_out, int rows_in, int t, long long cap, int d,
                     int dtype, void* stream);
+
+/* ---- Sampling search (csrc/sample.hip): the choice of one token per row for one decoding step.  pk_sample_select
+ * replaces, per step of sample_on_the_fly (pasero/decoding.py:1136-1190): the repeat penalty, `.float().log_softmax(-1)`,
+ * the blacklist, the finished-row mask, argmax / top-k / nucleus / plain sampling and the forced prompt token.
+ *   logits [B][ld]      fp32 / bf16 / fp16, ld >= V (16-byte loads when every row starts on a 16-byte boundary)
+ *   history [B][history_ld], n_hist   with penalty != 1: every DISTINCT token among the first n_hist of the row gets
+ *                       x = x < 0 ? x * penalty : x / penalty, rounded to the logits' dtype (padding tokens count)
+ *   inv_temperature     x *= inv_temperature after the penalty (fp32)
+ *   lp = (x - max) - log(sum exp(x - max)), fp32, over the whole row; then lp = -inf for blacklist[n_blacklist] ids and,
+ *   where finished[row] != 0 (or NULL = none), for everything but `pad`.  Masked tokens do not leave the normaliser.
+ *   mode 0 greedy   arg-max of lp, lowest id among equals; a row without a finite lp gives token 0
+ *        1 top-k    kept set = the top_k best (1 <= top_k <= V)       } in the order (probability descending, token id
+ *        2 top-p    kept set = every token whose inclusive cumulative  } ascending); c_i <= top_p plus the next one
+ *                   probability c_i <= top_p, plus the next one (0 < top_p < 1); all of V when no c_i exceeds top_p
+ *        3 full     kept set = every token with a finite lp
+ *   Modes 1-3 draw by inverse CDF: M = the kept set's total probability, the token is the first in that order whose
+ *   inclusive cumulative probability exceeds u * M.  u = uniform_in[row] when given (must lie in [0, 1)), else the
+ *   Philox draw described at the top of this file.  top_k > 0 together with top_p < 1 is refused in every mode.
+ *   forced [B * forced_stride] or NULL: a value other than `pad` replaces the chosen token.
+ *   token [B * token_stride] (int64; may be the memory `forced` points to), logprob [B] (the masked lp of the token
+ *   written; -inf for a masked token or one outside [0, V)), lse [B], n_kept [B] (top_k; the size of the nucleus; the number
+ *   of finite lp; 1 for greedy), kept_mass [B] (M; 0 for greedy), u_out [B] (the uniform used; 0 for greedy).
+ * Every output is a pure function of the inputs (probabilities are summed in 64-bit fixed point, 2^-62 units: integer
+ * sums do not depend on order).  V <= 2^27; B <= 65535.  NaN and +inf logits are undefined (the reference gives NaN
+ * probabilities for them); -inf is a token of probability 0.  Nothing beyond element V - 1 of a row is read.  `scratch` (device,
+ * 256-byte aligned) holds pk_sample_select_scratch(B, V) bytes.  Two launches on `stream`, no host synchronisation. */
+size_t pk_sample_select_scratch(int B, long long V);
+int pk_sample_select(const void* logits, long long ld, long long V, int B, int dtype, const long long* history,
+                     long long history_ld, int n_hist, float penalty, float inv_temperature, const long long* blacklist,
+                     int n_blacklist, const unsigned char* finished, long long pad, int mode, int top_k, float top_p,
+                     const float* uniform_in, unsigned long long seed, unsigned long long offset, const long long* forced,
+                     long long forced_stride, void* scratch, size_t scratch_bytes, long long* token,
+                     long long token_stride, float* logprob, float* lse, int* n_kept, float* kept_mass, float* u_out,
+                     void* stream);
 
 /* ---- "Next" row: feature collate.  Replaces the CPU pad_sequence + dtype cast of
  * utils.tokens_as_tensor for floating-point feature sequences (pasero/utils.py:709-736) as used on speech batches read

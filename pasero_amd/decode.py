@@ -10,6 +10,11 @@ What changes relative to the reference's incremental mode (pasero/models/modules
 The caches ride in the `state` dict under '_pk_decode' (`DecodeCache`); `Decoder.reorder_state` reorders them for beam
 search.  Layers the native step does not cover (subclass hooks, adapters, gated feed-forward, rotary positions) keep
 using the per-op path: `build_plan` returns None for them.
+
+Beam search (`beam_search`, `BeamSelect`): see the section below.  Sampling search (`search`, `sampling`,
+`sample_on_the_fly`, `SampleSelect`): the reference's other decoding arm (decoding.py:906-1221 — greedy, top-k, nucleus and
+plain sampling, repeat penalty, blacklist, prompts, stop sequences) with one pk_sample_select call per step and the stop
+test on the device; draws are inverse-CDF over (probability descending, token id ascending) from Philox(rng.next_offset()).
 """
 import ctypes
 import os
@@ -548,3 +553,197 @@ def beam_search(decoder, encoder_outputs, encoder_masks, max_output_len: int, be
             for h in nbest:
                 _uncollate(h, pad, None if src_mask is None else src_mask[b0])
     return output
+
+
+# ---- sampling search (pasero/decoding.py:906-1221) ---------------------------------------------------------------------
+SAMPLE_MODES = {'greedy': 0, 'topk': 1, 'topp': 2, 'full': 3}
+
+
+class SampleSelect:
+    """buffers of pk_sample_select for steps of up to B rows over V tokens, and the call itself.  After `run`:
+    `logprob`, `lse`, `kept_mass`, `u` (fp32) and `n_kept` (int32) hold rows [0, B); the tokens are in `token` (int64)
+    unless the caller gave a destination of its own (`out`: any int64 view with one element per row, e.g. a column)."""
+
+    def __init__(self, B: int, V: int, device):
+        L = lib.load()
+        self.B, self.V = B, V
+        self.scratch = torch.empty(max(256, L.pk_sample_select_scratch(B, V)), dtype=torch.uint8, device=device)
+        self.token = torch.zeros(B, dtype=torch.int64, device=device)
+        self.logprob, self.lse, self.kept_mass, self.u = (torch.zeros(B, dtype=torch.float32, device=device) for _ in range(4))
+        self.n_kept = torch.zeros(B, dtype=torch.int32, device=device)
+
+    def run(self, logits: Tensor, mode: str, *, top_k: int = 0, top_p: float = 1.0, history: Optional[Tensor] = None,
+            penalty: float = 1.0, inv_temperature: float = 1.0, blacklist: Optional[Tensor] = None,
+            finished: Optional[Tensor] = None, pad: int = -1, uniforms: Optional[Tensor] = None, seed: int = 0,
+            offset: int = 0, forced: Optional[Tensor] = None, out: Optional[Tensor] = None):
+        """logits (B, V), any row stride, fp32 / bf16 / fp16; history (B, n) int64 with unit column stride; forced / out:
+        int64, one element per row, any stride (they may be the same memory)"""
+        require_gpu(logits)
+        B = logits.size(0)
+        assert logits.dim() == 2 and logits.size(1) == self.V and B <= self.B
+        if logits.stride(1) != 1:
+            logits = logits.contiguous()
+        ld = logits.stride(0) if B > 1 else max(self.V, logits.stride(0))
+        for t, dt in ((history, torch.int64), (blacklist, torch.int64), (finished, torch.uint8), (uniforms, torch.float32),
+                      (forced, torch.int64), (out, torch.int64)):
+            assert t is None or (t.dtype == dt and t.is_cuda)
+        for t in (blacklist, finished, uniforms):
+            assert t is None or t.is_contiguous()
+        n_hist = hist_ld = 0
+        if history is not None and history.size(1) > 0:
+            assert history.dim() == 2 and history.size(0) == B and history.stride(1) == 1
+            n_hist, hist_ld = history.size(1), (history.stride(0) if B > 1 else max(history.size(1), history.stride(0)))
+        else:
+            history = None
+
+        def strided(t):
+            assert t.numel() == B
+            return t.stride(0) if t.dim() == 1 else t.stride(0) if t.size(1) == 1 else None
+        token = self.token if out is None else out
+        check(lib.load().pk_sample_select(
+            ptr(logits), ld, self.V, B, dtype_code(logits), ptr(history), hist_ld, n_hist, float(penalty),
+            float(inv_temperature), ptr(blacklist), 0 if blacklist is None else blacklist.numel(), ptr(finished), int(pad),
+            SAMPLE_MODES[mode], int(top_k), float(top_p), ptr(uniforms), int(seed), int(offset), ptr(forced),
+            0 if forced is None else strided(forced), ptr(self.scratch), self.scratch.numel(), ptr(token), strided(token),
+            ptr(self.logprob), ptr(self.lse), ptr(self.n_kept), ptr(self.kept_mass), ptr(self.u), stream_ptr()),
+            'pk_sample_select')
+
+
+def _single(decoder, encoder_outputs, encoder_masks, return_layers, sharded, who):
+    """the one decoder / encoder output / mask of a search, or NotImplementedError naming the option"""
+    if isinstance(encoder_outputs, (list, tuple)):
+        if len(encoder_outputs) > 1:
+            raise NotImplementedError(f'pasero_amd {who}: ensembles (several decoders) are not implemented')
+        encoder_outputs = encoder_outputs[0] if encoder_outputs else None
+    if isinstance(encoder_masks, (list, tuple)):
+        encoder_masks = encoder_masks[0] if encoder_masks else None
+    if len(getattr(decoder, 'decoders', ())) > 1:
+        raise NotImplementedError(f'pasero_amd {who}: ensembles (several decoders) are not implemented')
+    if return_layers:
+        raise NotImplementedError(f'pasero_amd {who}: return_layers is not implemented')
+    if sharded:
+        raise NotImplementedError(f'pasero_amd {who}: sharded=True is not implemented')
+    if encoder_outputs is None:
+        raise NotImplementedError(f'pasero_amd {who}: decoder-only models (empty encoder_outputs) are not implemented')
+    if getattr(decoder, 'decoders', None):  # a one-element ensemble wrapper
+        decoder = decoder.decoders[0]
+    return decoder, encoder_outputs, encoder_masks
+
+
+def sample_on_the_fly(decoder, encoder_outputs, encoder_masks, max_output_len: int, meta: dict, *,
+                      return_scores: bool = False, decoder_input: Optional[Tensor] = None,
+                      sampling_temperature: float = 1.0, sampling_topk: int = 0, sampling_topp: float = 1.0,
+                      return_layers=[], sharded: bool = False, device=None, repeat_penalty: float = 1.0, blacklist=[],
+                      stop_sequences=[], uniforms: Optional[Tensor] = None, **kwargs):
+    """Drop-in for pasero.decoding.sample_on_the_fly (decoding.py:1005-1221): same keyword signature, a generator that
+    yields {'tokens'[, 'pos_scores']} per step (the first yield covers a multi-token prompt).  The decoder call is the
+    reference's; between two decoder calls run ONE pk_sample_select (repeat penalty, log-softmax, blacklist, finished
+    rows, the choice, the forced prompt token, written straight into `tokens[:, step]`) and the stop test, on the device;
+    the only device->host read of a step is the all-finished flag.
+    Draws: inverse CDF in the order (probability descending, token id ascending) with one uniform per row and step —
+    Philox(seed, offset, row), `(seed, offset) = rng.next_offset()` once per step (seeded by `rng.manual_seed`, or lazily
+    from torch's global seed), or `uniforms[i]` (steps, B) for the i-th step when given (replaying a recorded search).
+    torch.multinomial's own stream is not reproduced.
+    Not implemented (raise, naming the option): ensembles, `return_layers`, `sharded`, decoder-only models."""
+    from . import rng
+    assert sampling_topk == 0 or sampling_topp == 1, 'combining nucleus sampling and top-k sampling is not allowed'
+    decoder, enc, enc_mask = _single(decoder, encoder_outputs, encoder_masks, return_layers, sharded, 'sample_on_the_fly')
+    decoder.eval()
+    dev = torch.device(device) if device is not None else enc.device
+    enc, enc_mask = enc.to(dev), None if enc_mask is None else enc_mask.to(dev)
+    require_gpu(enc)
+    B = enc.size(0)
+    pad, eos = decoder.padding_idx, decoder.eos_idx
+    if decoder_input is None:
+        decoder_input = torch.full((B, 1), decoder.bos_idx, dtype=torch.long, device=dev)
+    decoder_input = decoder_input.to(dev)
+    assert decoder_input.dim() == 2 and decoder_input.size(0) == B
+    plen = ((decoder_input != pad) * torch.arange(1, decoder_input.size(1) + 1, device=dev)).amax(dim=1)  # utils.mask_to_len
+    lo, hi = (int(x) for x in torch.stack([plen.min(), plen.max()]).tolist())  # (before the loop: not a step's read)
+    assert lo > 0
+    max_len = min(decoder.max_len, hi + max_output_len)
+    assert max_len >= 1
+    start = min(lo, max_len - 1)
+    tokens = torch.full((B, max_len), pad, dtype=torch.long, device=dev)
+    tokens[:, :decoder_input.size(1)] = decoder_input
+    stops = [s.to(dev) for s in stop_sequences if len(s) > 0] + [torch.tensor([eos], dtype=torch.long, device=dev)]
+    black = torch.tensor(list(blacklist), dtype=torch.int64, device=dev) if len(blacklist) else None
+    limit = plen + max_output_len
+    has_eos = torch.zeros(B, dtype=torch.bool, device=dev)
+    if sampling_temperature == 0 or sampling_topk == 1:
+        mode = 'greedy'
+    elif sampling_topk:
+        mode = 'topk'
+    elif sampling_topp < 1:
+        mode = 'topp'
+    else:
+        mode = 'full'
+    select, prev, state = None, 0, {}
+    with torch.no_grad():
+        for i, step in enumerate(range(start, max_len)):
+            has_eos = has_eos | (limit <= step)
+            logits, _ = decoder(enc, enc_mask, tokens[:, prev:step], state=state, meta=meta)
+            if select is None:
+                select = SampleSelect(B, logits.size(-1), dev)
+            seed, offset = rng.next_offset() if (uniforms is None and mode != 'greedy') else (0, 0)
+            # inv_temperature stays 1: the reference's single-decoder path never divides by the temperature (`t`,
+            # decoding.py:1131, is only used by the ensemble branch); `sampling_temperature` only selects greedy at 0
+            col = tokens[:, step:step + 1]  # forced where the prompt reaches this far (pad elsewhere), then the output
+            select.run(logits[:, -1], mode, top_k=sampling_topk if mode == 'topk' else 0,
+                       top_p=sampling_topp if mode == 'topp' else 1.0, history=tokens[:, :step], penalty=repeat_penalty,
+                       blacklist=black, finished=has_eos.view(torch.uint8), pad=pad,
+                       uniforms=None if uniforms is None else uniforms[i].to(dev, torch.float32).contiguous(),
+                       seed=seed, offset=offset, forced=col if step < hi else None, out=col)
+            out = {'tokens': tokens[:, prev + 1:step + 1]}
+            if return_scores:
+                last = -select.logprob[:B].clone().unsqueeze(1)
+                if logits.size(1) > 1:  # the first call carries the prompt: score its tokens with plain torch
+                    nxt = tokens[:, prev + 1:step]
+                    lp = logits[:, :-1].float().log_softmax(dim=-1).gather(2, nxt.unsqueeze(2)).squeeze(2)
+                    last = torch.cat([-lp, last], dim=1)
+                out['pos_scores'] = last
+            yield out
+            # the stop test (decoding.py:1208-1212) on the device; one host read: the all-finished flag
+            for s in stops:
+                if step + 1 >= len(s):
+                    has_eos = has_eos | (tokens[:, step + 1 - len(s):step + 1] == s).all(dim=1)
+            has_eos = has_eos & (plen <= step)  # EOS in the prompt does not count
+            prev = step
+            if bool(has_eos.all()):
+                break
+
+
+def sampling(decoder, encoder_outputs, encoder_masks, max_output_len: int, meta: dict, *,
+             decoder_input: Optional[Tensor] = None, enc_layer_outputs: dict = {}, **kwargs):
+    """Drop-in for pasero.decoding.sampling (decoding.py:942-1002): B one-element n-best lists of dicts ('tokens', and
+    under `return_scores` 'pos_scores' and 'score' = their sum), cut at the padding as the reference's `uncollate` does."""
+    src_mask = encoder_masks[0] if isinstance(encoder_masks, (list, tuple)) and encoder_masks else encoder_masks
+    if isinstance(src_mask, (list, tuple)):
+        src_mask = None
+    hyps = None
+    for out in sample_on_the_fly(decoder, encoder_outputs, encoder_masks, max_output_len, meta,
+                                 decoder_input=decoder_input, **kwargs):
+        for key, values in out.items():
+            if hyps is None:
+                hyps = [{} for _ in range(len(values))]
+            for i, value in enumerate(values):
+                hyps[i].setdefault(key, []).append(value)
+    pad = getattr(decoder, 'padding_idx')
+    for i, hyp in enumerate(hyps):
+        for k in hyp:
+            hyp[k] = torch.cat(hyp[k])
+        hyp.update({k: v[i] for k, v in enc_layer_outputs.items()})
+        _uncollate(hyp, pad, None if src_mask is None else src_mask[i])
+        if 'pos_scores' in hyp and 'score' not in hyp:
+            hyp['score'] = hyp['pos_scores'].sum()
+        hyps[i] = [hyp]
+    return hyps
+
+
+def search(*args, **kwargs):
+    """Drop-in for pasero.decoding.search (decoding.py:906-916): `sampling` unless beam search was asked for"""
+    if not kwargs.pop('sampling', False):
+        kwargs['sampling_temperature'] = 0
+    if kwargs.get('sampling_temperature', 1.0) > 0 or kwargs.get('beam_size', 1) <= 1:
+        return sampling(*args, **kwargs)
+    return beam_search(*args, **kwargs)

@@ -45,6 +45,9 @@ SIGNATURES = {
     'pk_beam_select_scratch': (SZ, [I, I, LL]),
     'pk_beam_select': (I, [P, LL, LL, I, I, I, P, P, P, LL, LL, P, I, P, P, SZ, P, P, P, P, P, P, P, P, P, P]),
     'pk_beam_reorder': (I, [P, P, P, P, I, P, I, I, I, LL, I, I, P]),
+    'pk_sample_select_scratch': (SZ, [I, LL]),
+    'pk_sample_select': (I, [P, LL, LL, I, I, P, LL, I, F, F, P, I, P, LL, I, I, F, P, ULL, ULL, P, LL, P, SZ, P, LL, P, P, P, P,
+                             P, P]),
     'pk_pad_rows': (I, [P, I, P, P, I, I, LL, I, P]),
     'pk_residual_ln_fwd': (I, [P, P, P, P, P, P, P, P, LL, I, F, F, ULL, ULL, I, P]),
     'pk_residual_ln_bwd_workspace': (SZ, [LL, I]),
