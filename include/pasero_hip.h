@@ -416,6 +416,48 @@ int pk_decoder_step(const PkDecoderPlan* plan, const long long* ids, int B, int 
 int pk_argmax_rows(const void* x, long long rows, long long n, long long ld, long long* out, long long out_stride,
                    int dtype, void* stream);
 
+/* ---- Bottleneck adapter on few rows (csrc/adapter.hip): the inference form of AdapterLayer.forward
+ * (pasero/models/modules.py:248-370), what a decoding step of `adapter_transformer` runs after every layer
+ * (pasero/models/adapters.py:232-301):
+ *   y = x + scaling * ( act( LN(x) down_w^T + down_b ) up_w^T + up_b )
+ * x, y [rows][d] (y may be x itself; any other overlap is refused), down_w [p][d], up_w [d][p]; ln_g == NULL: no
+ * LayerNorm; ln_b, down_b, up_b may be NULL; act: PK_ACT_*.  Rows >= `rows` are neither read nor written.  No allocation,
+ * no synchronisation.
+ * pk_adapter_rows_fused: 1 when the call runs as ONE fused launch — 16-bit dtype, d % 64 == 0, d <= 2048, p % 8 == 0,
+ * 8 <= p <= 512 and the 32-row tile (LN(x), the bottleneck tile, the K-split partials) fits 160 KiB of LDS; 0 when it
+ * runs as pk_residual_ln_fwd + pk_gemm + pk_gemm inside the same call through `scratch` (fp32, other sizes, or the
+ * environment variable PK_ADAPTER_FUSED=0, read when the library is loaded).
+ * pk_adapter_rows_scratch: bytes of `scratch` that call needs; 0 when it is fused. */
+int pk_adapter_rows_fused(long long rows, int d, int p, int dtype);
+size_t pk_adapter_rows_scratch(long long rows, int d, int p, int dtype);
+int pk_adapter_rows(const void* x, void* y, const void* ln_g, const void* ln_b, const void* down_w, const void* down_b,
+                    const void* up_w, const void* up_b, long long rows, int d, int p, int act, float scaling, float eps,
+                    int dtype, void* scratch, size_t scratch_bytes, void* stream);
+
+/* pk_decoder_step for decoders whose layers carry adapters (`adapter_transformer`): after the feed-forward block end of
+ * layer l the step applies adapters[l].a[0 .. n) in order (pk_adapter_rows) to its running activation.  `adapters`: a
+ * host array of plan->n_layers entries (n == 0: a layer without adapters), or NULL — then the call IS pk_decoder_step,
+ * launch for launch.  Every adapter has the plan's d and dtype. */
+#define PK_ADAPTER_STACK_MAX 4
+typedef struct {
+    const void *ln_g, *ln_b, *down_w, *down_b, *up_w, *up_b;
+    int p, act;
+    float scaling, eps;
+} PkAdapter;
+typedef struct {
+    int n;
+    PkAdapter a[PK_ADAPTER_STACK_MAX];
+} PkAdapterStack;
+/* pk_adapter_step_fused(on): which route the STEP's adapters take — 1: the fused kernel where pk_adapter_rows_fused says
+ * so, 0 (default; PK_ADAPTER_STEP_FUSED at library load): always the three launches, measured faster inside the step
+ * (docs/experiments.md).  on < 0 only asks.  Returns the previous setting.  The step's scratch covers both. */
+int pk_adapter_step_fused(int on);
+size_t pk_decoder_step_scratch_ex(const PkDecoderPlan* plan, int B, const PkAdapterStack* adapters);
+int pk_decoder_step_ex(const PkDecoderPlan* plan, const long long* ids, int B, int t, int pos_start, void* const* self_k,
+                       void* const* self_v, long long cap, const void* const* cross_kv, const unsigned char* enc_mask,
+                       int S, void* scratch, size_t scratch_bytes, void* logits, long long ld_logits,
+                       const PkAdapterStack* adapters, void* stream);
+
 /* ---- Beam search (csrc/beam.hip): the selection of one search step and the re-ordering of the native step's caches.
  * pk_beam_select replaces, per step of beam_search (pasero/decoding.py:1225-1657): `.float().log_softmax(-1)`, the
  * blacklist, the forced prompt tokens, `scores += hyp_scores`, `topk(2K)` over (B, K*V), the EOS mask and

@@ -28,6 +28,10 @@ int pk_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse
 int pk_embed_fwd(const long long* ids, const void* E, const void* pos, void* out, long long ntok, int Tlen, int d,
                  long long V, float scale, int pos_start, float drop_p, unsigned long long seed,
                  unsigned long long offset, int dtype, void* stream);
+size_t pk_adapter_rows_step_scratch(long long rows, int d, int p, int dtype);
+int pk_adapter_rows_step(const void* x, void* y, const void* ln_g, const void* ln_b, const void* down_w, const void* down_b,
+                    const void* up_w, const void* up_b, long long rows, int d, int p, int act, float scaling, float eps,
+                    int dtype, void* scratch, size_t scratch_bytes, void* stream);
 }
 
 // ---- plan: mirrors include/pasero_hip.h (PkDecoderLayerWeights / PkDecoderPlan) ----
@@ -54,6 +58,17 @@ struct PkDecoderPlan {
     const void* final_ln_b;
     const void* out_w;        // output projection [V][D] (the embedding itself when tied)
     const PkDecoderLayerWeights* layers;
+};
+// the adapters of a layer, applied in order after its feed-forward block end (adapters.py:232-301)
+#define PK_ADAPTER_STACK_MAX 4
+struct PkAdapter {
+    const void *ln_g, *ln_b, *down_w, *down_b, *up_w, *up_b;
+    int p, act;
+    float scaling, eps;
+};
+struct PkAdapterStack {
+    int n;
+    PkAdapter a[PK_ADAPTER_STACK_MAX];
 };
 
 namespace {
@@ -104,11 +119,12 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const T* __restrict__ 
 inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 struct Scratch {
-    char *x0, *x1, *h, *qkv, *q, *o, *ff;
+    char *x0, *x1, *h, *qkv, *q, *o, *ff, *ad;
     float *lse, *mean, *rstd;
-    size_t total;
+    size_t total, ad_bytes;
 };
-Scratch carve(const PkDecoderPlan* p, int B, char* base) {
+// `adapters` adds, behind everything else, the largest three-launch scratch one of them needs
+Scratch carve(const PkDecoderPlan* p, int B, char* base, const PkAdapterStack* adapters) {
     const size_t es = p->dtype == PK_F32 ? 4 : 2;
     Scratch s;
     size_t off = 0;
@@ -123,14 +139,24 @@ Scratch carve(const PkDecoderPlan* p, int B, char* base) {
     s.lse = (float*)take((size_t)B * p->heads * 4);
     s.mean = (float*)take((size_t)B * 4);
     s.rstd = (float*)take((size_t)B * 4);
+    s.ad_bytes = 0;
+    for (int l = 0; adapters && l < p->n_layers; ++l)
+        for (int i = 0; i < adapters[l].n && i < PK_ADAPTER_STACK_MAX; ++i) {
+            const size_t need = pk_adapter_rows_step_scratch(B, p->d, adapters[l].a[i].p, p->dtype);
+            if (need > s.ad_bytes) s.ad_bytes = need;
+        }
+    s.ad = take(s.ad_bytes);
     s.total = off;
     return s;
 }
 
 }  // namespace
 
+extern "C" size_t pk_decoder_step_scratch_ex(const PkDecoderPlan* plan, int B, const PkAdapterStack* adapters) {
+    return carve(plan, B > 0 ? B : 1, nullptr, adapters).total;
+}
 extern "C" size_t pk_decoder_step_scratch(const PkDecoderPlan* plan, int B) {
-    return carve(plan, B > 0 ? B : 1, nullptr).total;
+    return pk_decoder_step_scratch_ex(plan, B, nullptr);
 }
 
 #define RC(call)                 \
@@ -139,15 +165,22 @@ extern "C" size_t pk_decoder_step_scratch(const PkDecoderPlan* plan, int B) {
         if (rc_ != 0) return rc_; \
     } while (0)
 
-extern "C" int pk_decoder_step(const PkDecoderPlan* plan, const long long* ids, int B, int t, int pos_start,
-                               void* const* self_k, void* const* self_v, long long cap, const void* const* cross_kv,
-                               const unsigned char* enc_mask, int S, void* scratch, size_t scratch_bytes, void* logits,
-                               long long ld_logits, void* stream) {
+extern "C" int pk_decoder_step_ex(const PkDecoderPlan* plan, const long long* ids, int B, int t, int pos_start,
+                                  void* const* self_k, void* const* self_v, long long cap, const void* const* cross_kv,
+                                  const unsigned char* enc_mask, int S, void* scratch, size_t scratch_bytes, void* logits,
+                                  long long ld_logits, const PkAdapterStack* adapters, void* stream) {
     PK_CHECK_ARG(plan && ids && self_k && self_v && cross_kv && scratch && logits, "pk_decoder_step: null argument");
     PK_CHECK_ARG(B > 0 && t >= 0 && t < cap && S > 0, "pk_decoder_step: bad sizes (B=%d t=%d cap=%lld S=%d)", B, t, cap, S);
     PK_CHECK_ARG(plan->d % 64 == 0 && plan->heads * 64 == plan->d, "pk_decoder_step: head_dim must be 64");
     PK_CHECK_ARG(plan->dtype == PK_F32 || plan->dtype == PK_BF16 || plan->dtype == PK_F16, "pk_decoder_step: bad dtype");
-    Scratch s = carve(plan, B, (char*)scratch);
+    for (int l = 0; adapters && l < plan->n_layers; ++l) {
+        PK_CHECK_ARG(adapters[l].n >= 0 && adapters[l].n <= PK_ADAPTER_STACK_MAX, "pk_decoder_step: layer %d has %d adapters (0..%d)",
+                     l, adapters[l].n, PK_ADAPTER_STACK_MAX);
+        for (int i = 0; i < adapters[l].n; ++i)
+            PK_CHECK_ARG(adapters[l].a[i].down_w && adapters[l].a[i].up_w && adapters[l].a[i].p > 0,
+                         "pk_decoder_step: adapter %d of layer %d is incomplete", i, l);
+    }
+    Scratch s = carve(plan, B, (char*)scratch, adapters);
     PK_CHECK_ARG(scratch_bytes >= s.total, "pk_decoder_step: scratch too small (%zu < %zu)", scratch_bytes, s.total);
     const int D = plan->d, H = plan->heads, F = plan->ffn, dt = plan->dtype;
     const float scale = plan->scaled_attn ? 0.125f : 1.f;
@@ -212,6 +245,13 @@ extern "C" int pk_decoder_step(const PkDecoderPlan* plan, const long long* ids, 
         RC(linear(in, w.fc1_w, w.fc1_b, s.ff, F, D, plan->act));
         RC(linear(s.ff, w.fc2_w, w.fc2_b, s.q, D, F, PK_ACT_NONE));
         RC(block_end(s.q, w.ln3_g, w.ln3_b));
+        // ---- the layer's adapters (AdapterTransformerDecoderLayer.forward): x <- adapter(x), into the other buffer ----
+        for (int i = 0; adapters && i < adapters[l].n; ++i) {
+            const PkAdapter& ad = adapters[l].a[i];
+            RC(pk_adapter_rows_step(x, xn, ad.ln_g, ad.ln_b, ad.down_w, ad.down_b, ad.up_w, ad.up_b, B, D, ad.p, ad.act, ad.scaling,
+                               ad.eps, dt, s.ad, s.ad_bytes, stream));
+            std::swap(x, xn);
+        }
     }
     if (plan->final_ln_g) {
         RC(pk_residual_ln_fwd(x, nullptr, plan->final_ln_g, plan->final_ln_b, nullptr, xn, s.mean, s.rstd, B, D, plan->eps,
@@ -222,6 +262,14 @@ extern "C" int pk_decoder_step(const PkDecoderPlan* plan, const long long* ids, 
     RC(pk_gemm(x, plan->out_w, logits, nullptr, nullptr, nullptr, B, plan->vocab, D, D, D, ld_logits, 0, 0, 0, 0, PK_ACT_NONE,
                0, 1.f, dt, 1, nullptr, 0, nullptr, stream));
     return 0;
+}
+
+extern "C" int pk_decoder_step(const PkDecoderPlan* plan, const long long* ids, int B, int t, int pos_start,
+                               void* const* self_k, void* const* self_v, long long cap, const void* const* cross_kv,
+                               const unsigned char* enc_mask, int S, void* scratch, size_t scratch_bytes, void* logits,
+                               long long ld_logits, void* stream) {
+    return pk_decoder_step_ex(plan, ids, B, t, pos_start, self_k, self_v, cap, cross_kv, enc_mask, S, scratch, scratch_bytes,
+                              logits, ld_logits, nullptr, stream);
 }
 
 extern "C" int pk_argmax_rows(const void* x, long long rows, long long n, long long ld, long long* out,

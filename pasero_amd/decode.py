@@ -8,8 +8,10 @@ What changes relative to the reference's incremental mode (pasero/models/modules
     documents — (B, t, H, hd) tensors — as views of those buffers;
   * `k_proj/v_proj(encoder_out)` are computed once per sentence (the reference recomputes them at every step).
 The caches ride in the `state` dict under '_pk_decode' (`DecodeCache`); `Decoder.reorder_state` reorders them for beam
-search.  Layers the native step does not cover (subclass hooks, adapters, gated feed-forward, rotary positions) keep
-using the per-op path: `build_plan` returns None for them.
+search.  Layers the native step does not cover (subclass hooks, gated feed-forward, rotary positions) keep using the
+per-op path: `build_plan` returns None for them.  The layers of `adapter_transformer` (`AdapterTransformerDecoderLayer`,
+the IWSLT2023 recipes) are covered: the plan carries each layer's stack of adapters in use and the step applies them
+with pk_adapter_rows after the layer's feed-forward block (`pk_decoder_step_ex`).
 
 Beam search (`beam_search`, `BeamSelect`): see the section below.  Sampling search (`search`, `sampling`,
 `sample_on_the_fly`, `SampleSelect`): the reference's other decoding arm (decoding.py:906-1221 — greedy, top-k, nucleus and
@@ -44,12 +46,71 @@ class PkDecoderPlan(ctypes.Structure):
                 + [('layers', ctypes.POINTER(PkDecoderLayerWeights))])
 
 
-class Plan:
-    """the PkDecoderPlan of one TransformerDecoder plus what keeps its pointers alive / detects that they went stale"""
+PK_ADAPTER_STACK_MAX = 4
+_ADAPTER_FIELDS = ['ln_g', 'ln_b', 'down_w', 'down_b', 'up_w', 'up_b']
 
-    def __init__(self, c_plan, c_layers, keep, fingerprint, cross_w):
+
+class PkAdapter(ctypes.Structure):
+    _fields_ = ([(n, _P) for n in _ADAPTER_FIELDS] + [('p', ctypes.c_int), ('act', ctypes.c_int),
+                                                     ('scaling', ctypes.c_float), ('eps', ctypes.c_float)])
+
+
+class PkAdapterStack(ctypes.Structure):
+    _fields_ = [('n', ctypes.c_int), ('a', PkAdapter * PK_ADAPTER_STACK_MAX)]
+
+
+class Plan:
+    """the PkDecoderPlan of one TransformerDecoder plus what keeps its pointers alive / detects that they went stale;
+    `c_adapters`: the PkAdapterStack of every layer when some layer has adapters in use, else None"""
+
+    def __init__(self, c_plan, c_layers, keep, fingerprint, cross_w, c_adapters=None):
         self.c_plan, self.c_layers, self.keep, self.fingerprint, self.cross_w = c_plan, c_layers, keep, fingerprint, cross_w
+        self.c_adapters = c_adapters
         self.full = None
+
+    @property
+    def adapters_ref(self):
+        return None if self.c_adapters is None else ctypes.cast(self.c_adapters, _P)
+
+
+def _adapter_key(decoder):
+    """what `AdapterTransformerDecoder.forward` may change between two calls (it rewrites `adapters_in_use` from `meta`,
+    adapters.py:112-117) and `enable()` / `disable()`: per adapter layer, the names in use and their disabled flags.
+    None for a decoder without adapter layers: its keys stay what they were."""
+    key = None
+    for layer in decoder.layers:
+        names, ads = getattr(layer, 'adapters_in_use', None), getattr(layer, 'adapters', None)
+        if names is not None and ads is not None:  # (the decoder writes `adapters_in_use` on its plain layers too)
+            flags = tuple(bool(ads[u].disabled or ads[u].permanently_disabled) if u in ads else None for u in names)
+            key = (key or ()) + ((tuple(names), flags),)
+    return key
+
+
+def _adapter_stack(layer, D: int):
+    """[(tensors in _ADAPTER_FIELDS order, p, act, scaling, eps)] of the adapters `layer` applies, in order — None when the
+    native step cannot run them (more than PK_ADAPTER_STACK_MAX, no residual, another output width, an unknown name)"""
+    out = []
+    for uid in layer.adapters_in_use:
+        if uid not in layer.adapters:
+            return None  # (the per-op path raises the KeyError)
+        ad = layer.adapters[uid]
+        if ad.disabled or ad.permanently_disabled:
+            continue
+        if not ad.residual or ad.output_dim != ad.input_dim or ad.input_dim != D or ad.act_name not in ACT:
+            return None
+        norm = ad.layer_norm if ad.has_layer_norm else None
+        if norm is not None and (type(norm) is not torch.nn.LayerNorm or tuple(norm.normalized_shape) != (D,)
+                                 or norm.weight is None):
+            return None
+        p = ad.down.weight.size(0)
+        if tuple(ad.down.weight.shape) != (p, D) or tuple(ad.up.weight.shape) != (D, p):
+            return None
+        tensors = [getattr(norm, 'weight', None), getattr(norm, 'bias', None), ad.down.weight, ad.down.bias, ad.up.weight,
+                   ad.up.bias]
+        if any(t is not None and not t.is_contiguous() for t in tensors):
+            return None
+        out.append((tensors, p, ACT[ad.act_name], float(ad.scaling), float(getattr(norm, 'eps', 1e-5))))
+    return out if len(out) <= PK_ADAPTER_STACK_MAX else None
 
 
 def _fingerprint(decoder):
@@ -67,6 +128,7 @@ def _full_fingerprint(decoder):
 def build_plan(decoder) -> Optional[Plan]:
     """PkDecoderPlan for `decoder` (a pasero_amd TransformerDecoder), or None when a layer is not the stock one"""
     from . import modules
+    from .adapters import AdapterTransformerDecoderLayer
     from .transformer import TransformerDecoderLayer
     cfg = decoder.cfg
     if (decoder.training or not decoder.embed_tokens.weight.is_cuda
@@ -87,10 +149,21 @@ def build_plan(decoder) -> Optional[Plan]:
     def ln(m):
         return m if type(m) in (modules.LayerNorm, modules.WrappableLayerNorm, modules.LayerNormWithoutBias) else None
 
-    keep, layers = [], []
+    keep, layers, stacks = [], [], []
     for layer in decoder.layers:
-        if not isinstance(layer, TransformerDecoderLayer) or not layer._hooks_are_base(*hooks):
+        if not isinstance(layer, TransformerDecoderLayer):
             return None
+        if type(layer) is AdapterTransformerDecoderLayer:  # exactly: a subclass may do anything around its adapters
+            if not layer._hooks_are_base(*hooks[:-1]):
+                return None
+            stack = _adapter_stack(layer, cfg.embed_dim)
+            if stack is None:
+                return None
+            stacks.append(stack)
+        elif not layer._hooks_are_base(*hooks):
+            return None
+        else:
+            stacks.append([])
         if (getattr(layer, '_no_ckpt_forward', None) is not None or layer.fc3 is not None or layer.fc1.lora is not None
                 or layer.self_attn.q_proj.lora is not None):
             return None
@@ -135,10 +208,20 @@ def build_plan(decoder) -> Optional[Plan]:
     p.layers = ctypes.cast(c_layers, ctypes.POINTER(PkDecoderLayerWeights))
     keep += [t for vals, _ in layers for t in vals if t is not None] + [E, out_w]  # the pointers stay valid
     keep += [t for m in (embed_ln, final_ln) if not isinstance(m, modules.Identity) for t in (m.weight, m.bias)]
+    c_adapters = None
+    if any(stacks):
+        c_adapters = (PkAdapterStack * len(stacks))()
+        for cs, stack in zip(c_adapters, stacks):
+            cs.n = len(stack)
+            for ca, (tensors, rank, act, scaling, eps) in zip(cs.a, stack):
+                for name, v in zip(_ADAPTER_FIELDS, tensors):
+                    setattr(ca, name, ptr(v))
+                ca.p, ca.act, ca.scaling, ca.eps = rank, act, scaling, eps
+                keep += [t for t in tensors if t is not None]  # (and under the mixed-dtype rule below)
     dtypes = {t.dtype for t in keep if t is not None and t.is_floating_point()}
     if len(dtypes) != 1:
         return None  # mixed parameter dtypes (e.g. fp32 LayerNorm weights in a bf16 model): per-op path, which refuses loudly
-    plan = Plan(p, c_layers, keep, _fingerprint(decoder), [cw for _, cw in layers])
+    plan = Plan(p, c_layers, keep, _fingerprint(decoder), [cw for _, cw in layers], c_adapters)
     plan.full = _full_fingerprint(decoder)
     return plan
 
@@ -149,6 +232,9 @@ _plans = weakref.WeakKeyDictionary()  # decoder -> (fingerprint, training), Plan
 def get_plan(decoder) -> Optional[Plan]:
     """the decoder's plan, rebuilt when its parameters moved (`.to()`), changed dtype or it switched train/eval"""
     key = (_fingerprint(decoder), decoder.training)
+    ad_key = _adapter_key(decoder)
+    if ad_key is not None:  # (decoders without adapter layers keep the two-element key)
+        key += (ad_key,)
     cached = _plans.get(decoder)
     if cached is None or cached[0] != key:
         cached = (key, build_plan(decoder))
@@ -182,10 +268,15 @@ class DecodeCache:
         self.mask = None if encoder_mask is None else encoder_mask.contiguous()
         self.V = decoder.embed_tokens.weight.size(0)
         self.ldl = (self.V + 7) // 8 * 8
-        nbytes = lib.load().pk_decoder_step_scratch(ctypes.byref(plan.c_plan), B)
-        self.scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.scratch = torch.empty(self._scratch_bytes(B), dtype=torch.uint8, device=dev)
         self._tables()
         self._publish(state)
+
+    def _scratch_bytes(self, B: int) -> int:
+        L, plan = lib.load(), self.plan
+        if plan.c_adapters is None:
+            return L.pk_decoder_step_scratch(ctypes.byref(plan.c_plan), B)
+        return L.pk_decoder_step_scratch_ex(ctypes.byref(plan.c_plan), B, plan.adapters_ref)
 
     def _tables(self):
         n = len(self.names)
@@ -222,9 +313,12 @@ class DecodeCache:
         ids = ids.reshape(-1).contiguous()
         logits = torch.empty(self.B, self.ldl, device=self.scratch.device, dtype=self.k[0].dtype)  # the caller keeps it
         L = lib.load()
-        check(L.pk_decoder_step(ctypes.byref(self.plan.c_plan), ptr(ids), self.B, self.t, int(pos_start), self.k_tab,
-                                self.v_tab, self.cap, self.c_tab, ptr(self.mask), self.S, ptr(self.scratch),
-                                self.scratch.numel(), ptr(logits), self.ldl, stream_ptr()), 'pk_decoder_step')
+        args = (ctypes.byref(self.plan.c_plan), ptr(ids), self.B, self.t, int(pos_start), self.k_tab, self.v_tab, self.cap,
+                self.c_tab, ptr(self.mask), self.S, ptr(self.scratch), self.scratch.numel(), ptr(logits), self.ldl)
+        if self.plan.c_adapters is None:
+            check(L.pk_decoder_step(*args, stream_ptr()), 'pk_decoder_step')
+        else:
+            check(L.pk_decoder_step_ex(*args, self.plan.adapters_ref, stream_ptr()), 'pk_decoder_step_ex')
         self.t += 1
         self._publish(state)
         return logits[:, :self.V].unsqueeze(1)
@@ -238,7 +332,7 @@ class DecodeCache:
         self._spare = None
         self.cross = [c.view(-1, self.S, 2 * self.D).index_select(0, idx).view(-1, 2 * self.D) for c in self.cross]
         self.mask = None if self.mask is None else self.mask.index_select(0, idx)
-        nbytes = lib.load().pk_decoder_step_scratch(ctypes.byref(self.plan.c_plan), self.B)
+        nbytes = self._scratch_bytes(self.B)
         if nbytes > self.scratch.numel():
             self.scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.scratch.device)
         self._tables()

@@ -602,6 +602,37 @@ def argmax_rows(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     return out
 
 
+def adapter_rows_fused(rows: int, d: int, p: int, dtype) -> bool:
+    """whether `adapter_rows` on these sizes is the one fused launch (16-bit, d % 64 == 0, d <= 2048, p % 8 == 0, 8 <= p <= 512,
+    the tile fits the LDS) or the three-launch sequence inside the same call (include/pasero_hip.h)"""
+    code = {torch.float32: lib.PK_F32, torch.bfloat16: lib.PK_BF16, torch.float16: lib.PK_F16}[dtype]
+    return bool(lib.load().pk_adapter_rows_fused(rows, d, p, code))
+
+
+def adapter_rows(x: Tensor, ln_w: Optional[Tensor], ln_b: Optional[Tensor], down_w: Tensor, down_b: Optional[Tensor],
+                 up_w: Tensor, up_b: Optional[Tensor], act: str = 'relu', scaling: float = 1.0, eps: float = 1e-5,
+                 out: Optional[Tensor] = None) -> Tensor:
+    """y = x + scaling * (act(LN(x) down_w^T + down_b) up_w^T + up_b) for x (rows, d): one bottleneck adapter at inference
+    on few rows (a decoding step), pk_adapter_rows.  `out` may be x itself (in place).  Not differentiable, and not what
+    `AdapterLayer.forward` runs: that stays `autograd.AdapterFn`."""
+    require_gpu(x, ln_w, ln_b, down_w, down_b, up_w, up_b, out)
+    _same(x, ln_w, ln_b, down_w, down_b, up_w, up_b, out, what='adapter_rows')
+    assert x.dim() == 2 and x.is_contiguous() and down_w.is_contiguous() and up_w.is_contiguous()
+    rows, d = x.shape
+    p = down_w.size(0)
+    assert down_w.shape == (p, d) and up_w.shape == (d, p)
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.is_contiguous()
+    L = lib.load()
+    code = dtype_code(x)
+    nbytes = L.pk_adapter_rows_scratch(rows, d, p, code)
+    scratch = lib.workspace(nbytes, x.device, 'adapter') if nbytes else None
+    check(L.pk_adapter_rows(ptr(x), ptr(out), ptr(ln_w), ptr(ln_b), ptr(down_w), ptr(down_b), ptr(up_w), ptr(up_b), rows, d, p,
+                            ACT[act], float(scaling), float(eps), code, ptr(scratch), nbytes, stream_ptr()), 'pk_adapter_rows')
+    return out
+
+
 def mt_copy_plan(numels, device):
     """chunk list (device tensors) of a multi-tensor copy over tensors of `numels` elements (pk_mt_copy), plus the
     pointer table's home: a device tensor and two pinned host buffers that alternate between calls (the upload is an

@@ -42,6 +42,12 @@ SIGNATURES = {
     'pk_decoder_step_scratch': (SZ, [P, I]),
     'pk_decoder_step': (I, [P, P, I, I, I, P, P, LL, P, P, I, P, SZ, P, LL, P]),
     'pk_argmax_rows': (I, [P, LL, LL, LL, P, LL, I, P]),
+    'pk_adapter_rows_fused': (I, [LL, I, I, I]),
+    'pk_adapter_rows_scratch': (SZ, [LL, I, I, I]),
+    'pk_adapter_rows': (I, [P, P, P, P, P, P, P, P, LL, I, I, I, F, F, I, P, SZ, P]),
+    'pk_adapter_step_fused': (I, [I]),
+    'pk_decoder_step_scratch_ex': (SZ, [P, I, P]),
+    'pk_decoder_step_ex': (I, [P, P, I, I, I, P, P, LL, P, P, I, P, SZ, P, LL, P, P]),
     'pk_beam_select_scratch': (SZ, [I, I, LL]),
     'pk_beam_select': (I, [P, LL, LL, I, I, I, P, P, P, LL, LL, P, I, P, P, SZ, P, P, P, P, P, P, P, P, P, P]),
     'pk_beam_reorder': (I, [P, P, P, P, I, P, I, I, I, LL, I, I, P]),
