@@ -607,6 +607,63 @@ size_t pk_layer_fwd_ws(const PkLayer* layer);
 int pk_layer_bwd_sizes(const PkLayer* layer, size_t* scratch_bytes, size_t* ws_bytes);
 int pk_layer_bwd(const PkLayer* layer);
 
+/* ---- Mixture of experts (moe.hip): the `basic` layer of pasero/models/mixture_of_experts.py:32-75,141-190 with an fp32
+ * gate, as ROUTED computation — each token runs through its two experts only (the reference runs every expert over every
+ * token and multiplies by a mostly-zero weight, with one host read per expert).  Nothing below reads back to the host;
+ * every call checks its arguments before any launch.  S tokens, E experts (2 <= E <= 256), `pad` one byte per token
+ * (non-zero: padding) or NULL.  Row widths (D, F) are multiples of 8.
+ *
+ * pk_moe_gate: logits fp32 [S][E] ->
+ *   gate_value fp32 [S][E]  softmax over E; rows of padding tokens are 0
+ *   top_idx int32 [S][2]    the two best experts: higher fp32 gate value first, among EQUAL values the lower expert index
+ *                           (torch.topk leaves ties open); -1, -1 for padding tokens
+ *   top_w fp32 [S][2]       the two gate values normalised to sum 1; 0 for padding
+ *   top1_count int32 [E], prob_sum fp32 [E]  rank-1 counts and column sums of gate_value (fixed-order sums)
+ *   lb_coef fp32 [E], lb_loss fp32 [1]       lb_loss = E * sum_e (top1_count_e / n) (prob_sum_e / n), n = real tokens, and
+ *                           its derivative w.r.t. a real token's gate value of expert e (both 0 when n == 0, where the
+ *                           reference divides by zero)
+ *   offsets int32 [E+1]     expert e owns slots offsets[e] .. offsets[e+1]; offsets[E] = 2n
+ *   slot_of int32 [S][2]    the slot of pair (token, k); -1 for padding
+ *   token_of int32 [2S]     the token of every slot below offsets[E]: pairs sorted by expert, then token, then k (a stable
+ *                           counting sort: two calls give the same bits); entries beyond are not written
+ *   scratch: pk_moe_gate_scratch bytes (0 for sizes the call refuses).
+ * pk_moe_gate_bwd: d_logits fp32 [S][E] from d_top_w fp32 [S][2] (or NULL) and the load-balancing term
+ *   lb_scale * lb_scale_dev[0] * lb_coef[e] per real token (lb_coef NULL: none; lb_scale_dev NULL: 1), through the
+ *   normalisation, the top-2 mask and the softmax; rows of padding tokens are 0.
+ * pk_moe_gather: Xg[slot] = X[token_of[slot]] for slot < offsets[E], times top_w of that pair when top_w is given
+ *   (backward: dYs = top_w * dOut).  pk_moe_combine: out[token] = sum_k top_w[token][k] * Y[slot_of[token][k]] (top_w
+ *   NULL: plain sum — backward's dX), fixed order, no atomics, padding rows written as 0.  pk_moe_dot:
+ *   d_top_w[token][k] = <dOut[token], Y[slot_of[token][k]]> accumulated in fp32.
+ * pk_moe_gemm: ONE launch for all experts over slot-ordered buffers of `rows` (= 2S) rows; expert e's rows are
+ *   offsets[e] .. offsets[e+1], read on the device; the grid depends on rows and E alone, surplus workgroups exit; rows at
+ *   and beyond offsets[E] are neither read nor written.  W, bias: device arrays of E device pointers (bias may be NULL).
+ *     b_col = 0: C_e [.][N] = act(A_e W_e^T + b_e), W_e [N][K]        (mode 0; preact, if given, receives the value before act)
+ *     b_col = 1: C_e [.][N] = A_e W_e, W_e [K][N]                      (mode 0, or mode 2: times act'(aux), aux [rows][N])
+ * pk_moe_gemm_wgrad: dW_e [M][N] = dY_e^T X_e and db_e [M] = column sums of dY_e (dY [rows][M], X [rows][N]; dW / db:
+ *   device arrays of E device pointers, either may be NULL); an expert without rows gets zeros.
+ *   16-bit types run on MFMA with fp32 accumulation, fp32 on a plain kernel.
+ * pk_moe_use_grouped: 1 (default; env PK_MOE_GROUPED=0 sets the initial value) the model layer runs the grouped launches;
+ *   0: E pk_gemm launches with the counts read to the host (kept for comparison, docs/experiments.md); negative: query
+ *   only.  Returns the previous setting. */
+size_t pk_moe_gate_scratch(long long S, int E);
+int pk_moe_gate(const float* logits, const unsigned char* pad, long long S, int E, float* gate_value, int* top_idx,
+                float* top_w, int* top1_count, float* prob_sum, float* lb_coef, float* lb_loss, int* offsets, int* slot_of,
+                int* token_of, void* scratch, size_t scratch_bytes, void* stream);
+int pk_moe_gate_bwd(const float* d_top_w, const float* lb_coef, const float* lb_scale_dev, float lb_scale,
+                    const float* gate_value, const int* top_idx, float* d_logits, long long S, int E, void* stream);
+int pk_moe_gather(const void* X, void* Xg, const int* token_of, const int* offsets, const int* slot_of, const float* top_w,
+                  long long S, int E, int D, int dtype, void* stream);
+int pk_moe_combine(const void* Y, void* out, const int* slot_of, const float* top_w, long long S, int D, int dtype,
+                   void* stream);
+int pk_moe_dot(const void* dOut, const void* Y, const int* slot_of, float* d_top_w, long long S, int D, int dtype,
+               void* stream);
+int pk_moe_gemm(const void* A, const void* const* W, const void* const* bias, void* C, const void* aux, void* preact,
+                const int* offsets, long long rows, int E, long long N, long long K, int b_col, int act, int mode, int dtype,
+                void* stream);
+int pk_moe_gemm_wgrad(const void* dY, const void* X, void* const* dW, void* const* db, const int* offsets, long long rows,
+                      int E, long long M, long long N, int dtype, void* stream);
+int pk_moe_use_grouped(int on);
+
 #ifdef __cplusplus
 }
 #endif

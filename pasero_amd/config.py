@@ -300,3 +300,44 @@ class SyntheticTask:
 
     def remap_decoder_embed(self, embed):
         return embed
+
+
+@dataclass
+class _MOEOptions:   # config.py:1419-1466 (the options `moe_transformer` adds to a backbone configuration)
+    encoder_expert_count: object = 4          # int, or {layer id: count}
+    decoder_expert_count: object = 4
+    encoder_expert_dim: Optional[int] = None  # default: the feed-forward width of the stack
+    decoder_expert_dim: Optional[int] = None
+    encoder_expert_layer_ids: Optional[list] = None
+    decoder_expert_layer_ids: Optional[list] = None
+    encoder_expert_interval: int = 1
+    decoder_expert_interval: int = 1
+    moe_impl: str = 'basic'
+    capacity_factor: float = 0.0
+    load_balancing: float = 0.0
+    _arch = 'moe_transformer'
+
+
+@register_model_config('moe_transformer')
+@dataclass
+class MOETransformerConfig(_MOEOptions, TransformerConfig):
+    pass
+
+
+# moe_* presets (config.py:2511-2521)
+@register_model_config('moe_transformer_small')
+@dataclass
+class MOETransformerSmallConfig(_MOEOptions, TransformerSmallConfig):
+    pass
+
+
+@register_model_config('moe_transformer_big')
+@dataclass
+class MOETransformerBigConfig(_MOEOptions, TransformerBigConfig):
+    pass
+
+
+@register_model_config('moe_transformer_wide')
+@dataclass
+class MOETransformerWideConfig(_MOEOptions, TransformerWideConfig):
+    pass

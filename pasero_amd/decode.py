@@ -115,7 +115,10 @@ def _adapter_stack(layer, D: int):
 
 def _fingerprint(decoder):
     w = decoder.embed_tokens.weight
-    return (w.data_ptr(), w.dtype, str(w.device), decoder.layers[0].fc1.weight.data_ptr())
+    first = decoder.layers[0]
+    fc1 = getattr(first, 'fc1', None)  # (a mixture-of-experts layer has no fc1: any parameter of the layer serves as the anchor)
+    anchor = fc1.weight if fc1 is not None else next(first.parameters())
+    return (w.data_ptr(), w.dtype, str(w.device), anchor.data_ptr())
 
 
 def _full_fingerprint(decoder):

@@ -676,3 +676,134 @@ def mt_copy(srcs, dsts, plan) -> None:
     plan['uploaded'][turn] = ev
     check(lib.load().pk_mt_copy(ptr(plan['table']), n, ptr(plan['ct']), ptr(plan['cs']), plan['ct'].numel(),
                                 dtype_code(dsts[0]), stream_ptr()), 'pk_mt_copy')
+
+
+# ---- mixture of experts (csrc/moe.hip; autograd in pasero_amd.moe.MoEFn) ----
+class MoeRouting:
+    """what pk_moe_gate writes for one call: gate values, the top-2 choice and the routing tables, all on the device"""
+    __slots__ = ('gate_value', 'top_idx', 'top_w', 'top1_count', 'prob_sum', 'lb_coef', 'lb_loss', 'offsets', 'slot_of',
+                 'token_of')
+
+
+def moe_gate_scratch(S: int, E: int) -> int:
+    return int(lib.load().pk_moe_gate_scratch(S, E))
+
+
+def moe_gate(logits: Tensor, pad: Optional[Tensor]) -> MoeRouting:
+    """softmax over E, top-2 (lower index among equal values), normalised weights, load-balancing statistics and the
+    routing tables of include/pasero_hip.h:pk_moe_gate for fp32 `logits` (S, E) and a bool / uint8 padding mask (S,)"""
+    require_gpu(logits, pad)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
+    S, E = logits.shape
+    dev = logits.device
+    if pad is not None:
+        pad = pad.view(torch.uint8) if pad.dtype == torch.bool else pad
+        assert pad.dtype == torch.uint8 and pad.numel() == S and pad.is_contiguous()
+    r = MoeRouting()
+    r.gate_value = torch.empty(S, E, dtype=torch.float32, device=dev)
+    r.top_idx = torch.empty(S, 2, dtype=torch.int32, device=dev)
+    r.top_w = torch.empty(S, 2, dtype=torch.float32, device=dev)
+    r.top1_count = torch.empty(E, dtype=torch.int32, device=dev)
+    r.prob_sum = torch.empty(E, dtype=torch.float32, device=dev)
+    r.lb_coef = torch.empty(E, dtype=torch.float32, device=dev)
+    r.lb_loss = torch.empty((), dtype=torch.float32, device=dev)
+    r.offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
+    r.slot_of = torch.empty(S, 2, dtype=torch.int32, device=dev)
+    r.token_of = torch.empty(2 * S, dtype=torch.int32, device=dev)
+    L = lib.load()
+    nbytes = L.pk_moe_gate_scratch(S, E)
+    scratch = lib.workspace(nbytes, dev, 'moe_gate')
+    check(L.pk_moe_gate(ptr(logits), ptr(pad), S, E, ptr(r.gate_value), ptr(r.top_idx), ptr(r.top_w), ptr(r.top1_count),
+                        ptr(r.prob_sum), ptr(r.lb_coef), ptr(r.lb_loss), ptr(r.offsets), ptr(r.slot_of), ptr(r.token_of),
+                        ptr(scratch), nbytes, stream_ptr()), 'pk_moe_gate')
+    return r
+
+
+def moe_gate_bwd(d_top_w: Optional[Tensor], r: MoeRouting, lb_scale_dev: Optional[Tensor] = None,
+                 lb_scale: float = 0.0) -> Tensor:
+    """d logits fp32 (S, E); the load-balancing term enters with weight lb_scale * lb_scale_dev (a 0-d fp32 device tensor)"""
+    require_gpu(d_top_w, lb_scale_dev)
+    S, E = r.gate_value.shape
+    if d_top_w is not None:
+        assert d_top_w.dtype == torch.float32 and d_top_w.shape == (S, 2) and d_top_w.is_contiguous()
+    if lb_scale_dev is not None:
+        assert lb_scale_dev.dtype == torch.float32 and lb_scale_dev.numel() == 1
+    use_lb = lb_scale != 0.0
+    out = torch.empty(S, E, dtype=torch.float32, device=r.gate_value.device)
+    check(lib.load().pk_moe_gate_bwd(ptr(d_top_w), ptr(r.lb_coef) if use_lb else None, ptr(lb_scale_dev), float(lb_scale),
+                                     ptr(r.gate_value), ptr(r.top_idx), ptr(out), S, E, stream_ptr()), 'pk_moe_gate_bwd')
+    return out
+
+
+def moe_gather(x: Tensor, r: MoeRouting, scaled: bool = False) -> Tensor:
+    """token order (S, D) -> slot order (2S, D); rows at and beyond offsets[E] are left unwritten.  scaled: times top_w"""
+    require_gpu(x)
+    assert x.dim() == 2 and x.is_contiguous()
+    S, D = x.shape
+    E = r.offsets.numel() - 1
+    out = torch.empty(2 * S, D, dtype=x.dtype, device=x.device)
+    check(lib.load().pk_moe_gather(ptr(x), ptr(out), ptr(r.token_of), ptr(r.offsets), ptr(r.slot_of),
+                                   ptr(r.top_w) if scaled else None, S, E, D, dtype_code(x), stream_ptr()), 'pk_moe_gather')
+    return out
+
+
+def moe_combine(y: Tensor, r: MoeRouting, weighted: bool = True) -> Tensor:
+    """slot order (2S, D) -> token order (S, D): the (weighted) sum of a token's two slots; padding rows are 0"""
+    require_gpu(y)
+    assert y.dim() == 2 and y.is_contiguous()
+    S, D = y.size(0) // 2, y.size(1)
+    out = torch.empty(S, D, dtype=y.dtype, device=y.device)
+    check(lib.load().pk_moe_combine(ptr(y), ptr(out), ptr(r.slot_of), ptr(r.top_w) if weighted else None, S, D,
+                                    dtype_code(y), stream_ptr()), 'pk_moe_combine')
+    return out
+
+
+def moe_dot(d_out: Tensor, y: Tensor, r: MoeRouting) -> Tensor:
+    """d top_w (S, 2) fp32 = <d_out[token], y[slot_of[token][k]]>"""
+    require_gpu(d_out, y)
+    _same(d_out, y, what='moe_dot')
+    assert d_out.dim() == 2 and d_out.is_contiguous() and y.is_contiguous() and y.shape == (2 * d_out.size(0), d_out.size(1))
+    S, D = d_out.shape
+    out = torch.empty(S, 2, dtype=torch.float32, device=y.device)
+    check(lib.load().pk_moe_dot(ptr(d_out), ptr(y), ptr(r.slot_of), ptr(out), S, D, dtype_code(y), stream_ptr()), 'pk_moe_dot')
+    return out
+
+
+def moe_gemm(a: Tensor, w_ptrs: Tensor, offsets: Tensor, n: int, *, bias_ptrs: Optional[Tensor] = None, b_col: bool = False,
+             act: str = 'none', aux: Optional[Tensor] = None, mode: int = 0, preact: Optional[Tensor] = None,
+             out: Optional[Tensor] = None) -> Tensor:
+    """the grouped GEMM over slot-ordered `a` (rows, K): expert e's rows times its own weight (`w_ptrs`: int64 device tensor
+    of E data pointers to (n, K) weights, or (K, n) when b_col).  See include/pasero_hip.h:pk_moe_gemm."""
+    require_gpu(a, w_ptrs, offsets, bias_ptrs, aux, preact, out)
+    assert a.dim() == 2 and a.is_contiguous() and w_ptrs.dtype == torch.int64 and offsets.dtype == torch.int32
+    rows, K = a.shape
+    E = offsets.numel() - 1
+    assert w_ptrs.numel() == E and (bias_ptrs is None or bias_ptrs.numel() == E)
+    if out is None:
+        out = torch.empty(rows, n, dtype=a.dtype, device=a.device)
+    assert out.shape == (rows, n) and out.dtype == a.dtype and out.is_contiguous()
+    for t in (aux, preact):
+        assert t is None or (t.shape == (rows, n) and t.dtype == a.dtype and t.is_contiguous())
+    check(lib.load().pk_moe_gemm(ptr(a), ptr(w_ptrs), ptr(bias_ptrs), ptr(out), ptr(aux), ptr(preact), ptr(offsets), rows, E, n,
+                                 K, int(b_col), ACT[act], mode, dtype_code(a), stream_ptr()), 'pk_moe_gemm')
+    return out
+
+
+def moe_gemm_wgrad(dy: Tensor, x: Optional[Tensor], offsets: Tensor, dw_ptrs: Optional[Tensor],
+                   db_ptrs: Optional[Tensor]) -> None:
+    """dW_e (M, N) = dy_e^T x_e and db_e = colsum(dy_e) into the tensors `dw_ptrs` / `db_ptrs` (int64 device tensors of E data
+    pointers) point to; an expert without rows gets zeros"""
+    require_gpu(dy, x, offsets, dw_ptrs, db_ptrs)
+    _same(dy, x, what='moe_gemm_wgrad')
+    assert dy.dim() == 2 and dy.is_contiguous() and offsets.dtype == torch.int32
+    rows, M = dy.shape
+    N = x.size(1) if x is not None else M
+    assert x is None or (x.is_contiguous() and x.size(0) == rows)
+    E = offsets.numel() - 1
+    check(lib.load().pk_moe_gemm_wgrad(ptr(dy), ptr(x), ptr(dw_ptrs), ptr(db_ptrs), ptr(offsets), rows, E, M, N, dtype_code(dy),
+                                       stream_ptr()), 'pk_moe_gemm_wgrad')
+
+
+def moe_use_grouped(on: int = -1) -> bool:
+    """the route of the model layer's expert GEMMs (include/pasero_hip.h:pk_moe_use_grouped); returns the previous setting"""
+    return bool(lib.load().pk_moe_use_grouped(int(on)))

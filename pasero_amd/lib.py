@@ -99,6 +99,15 @@ SIGNATURES = {
     'pk_layer_bwd': (I, [P]),
     'pk_logmel_workspace': (SZ, [I]),
     'pk_logmel': (I, [P, P, LL, P, P, SZ, I, P]),
+    'pk_moe_gate_scratch': (SZ, [LL, I]),
+    'pk_moe_gate': (I, [P, P, LL, I, P, P, P, P, P, P, P, P, P, P, P, SZ, P]),
+    'pk_moe_gate_bwd': (I, [P, P, P, F, P, P, P, LL, I, P]),
+    'pk_moe_gather': (I, [P, P, P, P, P, P, LL, I, I, I, P]),
+    'pk_moe_combine': (I, [P, P, P, P, LL, I, I, P]),
+    'pk_moe_dot': (I, [P, P, P, P, LL, I, I, P]),
+    'pk_moe_gemm': (I, [P, P, P, P, P, P, P, LL, I, LL, LL, I, I, I, I, P]),
+    'pk_moe_gemm_wgrad': (I, [P, P, P, P, P, LL, I, LL, LL, I, P]),
+    'pk_moe_use_grouped': (I, [I]),
 }
 
 PK_WGRAD_MAX = 8
