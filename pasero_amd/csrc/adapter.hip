@@ -248,8 +248,6 @@ const bool g_fused_on = [] { const char* e = getenv("PK_ADAPTER_FUSED"); return 
 // 32-column blocks per workgroup of the up-projection (0: one workgroup per tile); default 4 = one block per wave
 const int g_slice_blocks = [] { const char* e = getenv("PK_ADAPTER_SLICE_BLOCKS"); return e ? atoi(e) : 4; }();
 
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 struct Fallback {
     char *h, *a, *sb;
     float *mean, *rstd;
@@ -258,14 +256,13 @@ struct Fallback {
 Fallback carve(long long rows, int d, int p, int dtype, char* base) {
     const size_t es = dtype == PK_F32 ? 4 : 2;
     Fallback f;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = base ? base + off : nullptr; off += align256(bytes); return q; };
-    f.h = take((size_t)rows * d * es);
-    f.a = take((size_t)rows * p * es);
-    f.sb = take((size_t)d * es);
-    f.mean = (float*)take((size_t)rows * 4);
-    f.rstd = (float*)take((size_t)rows * 4);
-    f.total = off;
+    Carve c{base};
+    f.h = c.take((size_t)rows * d * es);
+    f.a = c.take((size_t)rows * p * es);
+    f.sb = c.take((size_t)d * es);
+    f.mean = c.take<float>((size_t)rows * 4);
+    f.rstd = c.take<float>((size_t)rows * 4);
+    f.total = c.total;
     return f;
 }
 

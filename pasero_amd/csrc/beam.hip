@@ -7,8 +7,8 @@
 // `Decoder.reorder_state` (pasero/models/transformer.py:68-75).
 //
 // pk_beam_select reads the logits once, in their own dtype:
-//   pass 1  grid (chunks of V, rows), one WAVE per (row, chunk of 2048): 16-byte loads straight to registers (the
-//           operand is used once: no LDS), the chunk's (max, sum exp) and its top 2K RAW logits — log_softmax is
+//   pass 1  grid (chunks of V, rows), one WAVE per (row, chunk of 2048): the row scan of vocab_scan.h (chunk loader,
+//           slot mapping, the chunk's (max, sum exp)) and the chunk's top 2K RAW logits — log_softmax is
 //           monotone within a row and no (row, chunk) can own more than 2K of a sentence's 2K winners.  The top 2K are
 //           taken by 2K rounds of a wave-wide arg-max over each lane's cached best; only the winning lane rescans.
 //   pass 2  one workgroup per sentence: folds the chunks' (max, sum) into each row's log-sum-exp, rescores the
@@ -20,38 +20,14 @@
 // Known corner: pass 1 ranks by the raw logit, pass 2 by the rounded fp32 score.  Two DIFFERENT logits of one row whose
 // scores round to the same float are ranked by index in pass 2; if such a pair straddles position 2K of its own
 // (row, chunk) the one pass 1 dropped cannot come back.  Equal logits (the ties 16-bit inputs produce) are exact.
-#include <math.h>
-#include "common.h"
+#include "vocab_scan.h"
 
 namespace {
 
 constexpr int BEAM_MAX_K = 16;
-constexpr int P1_E = 32;               // logits per lane
-constexpr int P1_CHUNK = 64 * P1_E;    // logits per wave
 constexpr int P1_WAVES = 4;            // waves (= chunks) per workgroup
 constexpr int P2_THREADS = 1024;
 constexpr int REORDER_MAX_LAYERS = 48;
-
-// float -> unsigned whose integer order is the float order (-inf lowest); +0 and -0 are made one value first
-__device__ __forceinline__ unsigned ordered_bits(float f) {
-    unsigned u = __float_as_uint(f + 0.0f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ordered_float(unsigned o) {
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-// larger key = better candidate: score first, then the LOWER index
-__device__ __forceinline__ unsigned long long make_key(float score, unsigned index) {
-    return ((unsigned long long)ordered_bits(score) << 32) | (unsigned long long)(0xffffffffu - index);
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        unsigned long long o = __shfl_xor(k, off, 64);
-        k = o > k ? o : k;
-    }
-    return k;
-}
 
 struct P1Args {
     const void* logits;
@@ -68,8 +44,6 @@ struct P1Args {
 
 template <typename T, bool ALIGNED>
 __global__ __launch_bounds__(64 * P1_WAVES) void beam_pass1_kernel(P1Args a) {
-    constexpr int EPV = 16 / sizeof(T);
-    constexpr int NL = P1_E / EPV;
     const int lane = threadIdx.x & 63;
     const int chunk = blockIdx.x * P1_WAVES + (threadIdx.x >> 6);
     const int row = blockIdx.y;
@@ -77,72 +51,31 @@ __global__ __launch_bounds__(64 * P1_WAVES) void beam_pass1_kernel(P1Args a) {
     if (a.first_step && (row % a.K) != 0) return;       // scores[::beam_size] (decoding.py:1423-1425)
     const int R = 2 * a.K;
     const T* p = (const T*)a.logits + (long long)row * a.ld;
-    const int base = chunk * P1_CHUNK;
-
-    // slot s = j * EPV + e holds token base + (j * 64 + lane) * EPV + e: ascending in s within a lane
-    float v[P1_E];
-    unsigned gone = 0;  // bit s: slot s is out of the row or already taken
-#pragma unroll
-    for (int j = 0; j < NL; ++j) {
-        const int i0 = base + (j * 64 + lane) * EPV;
-        if constexpr (ALIGNED) {
-            if (i0 < a.V) {
-                Vec16<T> q = load16<T>(p + i0);
-#pragma unroll
-                for (int e = 0; e < EPV; ++e) v[j * EPV + e] = (i0 + e < a.V) ? q.get(e) + 0.0f : -INFINITY;
-            } else {
-#pragma unroll
-                for (int e = 0; e < EPV; ++e) v[j * EPV + e] = -INFINITY;
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < EPV; ++e) v[j * EPV + e] = (i0 + e < a.V) ? to_f32(p[i0 + e]) + 0.0f : -INFINITY;
-        }
-#pragma unroll
-        for (int e = 0; e < EPV; ++e)
-            if (i0 + e >= a.V) gone |= 1u << (j * EPV + e);
-    }
+    const int base = chunk * SCAN_CHUNK;
+    float v[SCAN_E];
+    unsigned gone;
+    load_chunk<T, ALIGNED>(p, a.V, base, lane, v, gone);  // bit s: slot s is out of the row or already taken
 
     // ---- the chunk's share of the row's softmax: (max, sum exp(x - max)) over the unmasked logits ----
-    float m = -INFINITY;
-#pragma unroll
-    for (int s = 0; s < P1_E; ++s) m = fmaxf(m, v[s]);
-    float sum = 0.f;
-    if (m != -INFINITY) {
-#pragma unroll
-        for (int s = 0; s < P1_E; ++s) sum += expf(v[s] - m);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float m2 = __shfl_xor(m, off, 64), s2 = __shfl_xor(sum, off, 64);
-        const float M = fmaxf(m, m2);
-        const float f1 = (m == -INFINITY) ? 0.f : expf(m - M), f2 = (m2 == -INFINITY) ? 0.f : expf(m2 - M);
-        sum = sum * f1 + s2 * f2;
-        m = M;
-    }
-    if (lane == 0) a.ms[(long long)row * a.nchunks + chunk] = make_float2(m, sum);
+    const float2 ms = chunk_max_sum(v);
+    if (lane == 0) a.ms[(long long)row * a.nchunks + chunk] = ms;
 
     // ---- what may not be chosen: blacklisted ids, and on a forced row everything but the forced token ----
     if (a.forced) {
         const long long f = a.forced[row];
         if (f != a.pad && f != a.eos) {
 #pragma unroll
-            for (int s = 0; s < P1_E; ++s) {
-                const int tok = base + ((s / EPV) * 64 + lane) * EPV + (s % EPV);
-                if (tok != f) v[s] = -INFINITY;
-            }
+            for (int s = 0; s < SCAN_E; ++s)
+                if (slot_token<T>(base, lane, s) != f) v[s] = -INFINITY;
         }
     }
     for (int b = 0; b < a.n_black; ++b) {
         const long long id = a.blacklist[b];
-        if (id < base || id >= (long long)base + P1_CHUNK) continue;  // wave-uniform
-        const int rel = (int)(id - base);
-        const int slot = (rel / (64 * EPV)) * EPV + rel % EPV;
-        if (lane == (rel / EPV) % 64) {
+        if (id < base || id >= (long long)base + SCAN_CHUNK) continue;  // wave-uniform
+        const unsigned hit = slot_bit<T>((int)(id - base), lane);
 #pragma unroll
-            for (int s = 0; s < P1_E; ++s)
-                if (s == slot) v[s] = -INFINITY;
-        }
+        for (int s = 0; s < SCAN_E; ++s)
+            if ((hit >> s) & 1u) v[s] = -INFINITY;
     }
 
     // ---- top 2K of the chunk: 2K rounds of a wave-wide arg-max over each lane's best; lane r keeps winner r ----
@@ -152,7 +85,7 @@ __global__ __launch_bounds__(64 * P1_WAVES) void beam_pass1_kernel(P1Args a) {
         bv = -INFINITY;
         bs = -1;
 #pragma unroll
-        for (int s = 0; s < P1_E; ++s) {
+        for (int s = 0; s < SCAN_E; ++s) {
             const bool live = !((gone >> s) & 1u);
             if (live && (bs < 0 || v[s] > bv)) { bv = v[s]; bs = s; }
         }
@@ -162,12 +95,12 @@ __global__ __launch_bounds__(64 * P1_WAVES) void beam_pass1_kernel(P1Args a) {
     int out_i = 0;
     for (int r = 0; r < R; ++r) {
         unsigned long long key = 0;
-        if (bs >= 0) key = make_key(bv, (unsigned)(((bs / EPV) * 64 + lane) * EPV + (bs % EPV)));
+        if (bs >= 0) key = rank_key(bv, (unsigned)slot_token<T>(0, lane, bs));
         const unsigned long long w = wave_max_u64(key);
         if (w != 0) {
             if (lane == r) {
-                out_x = ordered_float((unsigned)(w >> 32));
-                out_i = base + (int)(0xffffffffu - (unsigned)w);
+                out_x = key_score(w);
+                out_i = base + (int)key_index(w);
             }
             if (key == w) {  // one lane: the index is part of the key
                 gone |= 1u << bs;
@@ -207,23 +140,11 @@ __global__ __launch_bounds__(P2_THREADS) void beam_pass2_kernel(P2Args a) {
 
     // ---- each row's log-sum-exp from its chunks ----
     for (int k = wave; k < nrows; k += P2_THREADS / 64) {
-        const float2* ms = a.ms + (long long)(b * K + k) * a.nchunks;
-        float M = -INFINITY;
-        for (int c = lane; c < a.nchunks; c += 64) M = fmaxf(M, ms[c].x);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) M = fmaxf(M, __shfl_xor(M, off, 64));
-        double S = 0.0;
-        for (int c = lane; c < a.nchunks; c += 64) {
-            const float2 e = ms[c];
-            if (e.x != -INFINITY) S += (double)e.y * exp((double)e.x - (double)M);
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) S += __shfl_xor(S, off, 64);
+        const float2 f = fold_chunks(a.ms + (long long)(b * K + k) * a.nchunks, a.nchunks, lane);
         if (lane == 0) {
-            const float ls = S > 0.0 ? (float)log(S) : 0.f;
-            row_max[k] = M;
-            row_logsum[k] = ls;
-            if (a.lse_out) a.lse_out[b * K + k] = M + ls;
+            row_max[k] = f.x;
+            row_logsum[k] = f.y;
+            if (a.lse_out) a.lse_out[b * K + k] = f.x + f.y;
         }
     }
     __syncthreads();
@@ -237,7 +158,7 @@ __global__ __launch_bounds__(P2_THREADS) void beam_pass2_kernel(P2Args a) {
         float s = (a.cand_x[src] - row_max[k]) - row_logsum[k];
         if (a.row_bias) s += a.row_bias[row];
         if (a.hyp_in) s += a.hyp_in[row];
-        keys[c] = make_key(s, (unsigned)k * (unsigned)a.V + (unsigned)a.cand_i[src]);
+        keys[c] = rank_key(s, (unsigned)k * (unsigned)a.V + (unsigned)a.cand_i[src]);
     }
     __syncthreads();  // a thread rescans only its own keys, but keep the phases apart
 
@@ -280,8 +201,8 @@ __global__ __launch_bounds__(P2_THREADS) void beam_pass2_kernel(P2Args a) {
             float score = -INFINITY;
             int k = 0, tok = 0;
             if (w != 0) {
-                score = ordered_float((unsigned)(w >> 32));
-                const unsigned flat = 0xffffffffu - (unsigned)w;
+                score = key_score(w);
+                const unsigned flat = key_index(w);
                 k = (int)(flat / (unsigned)a.V);
                 tok = (int)(flat % (unsigned)a.V);
             }
@@ -324,9 +245,6 @@ __global__ __launch_bounds__(256) void beam_reorder_kernel(ReorderArgs a, const 
         *reinterpret_cast<uint4*>(dst + o) = *reinterpret_cast<const uint4*>(src + o);
 }
 
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-inline int n_chunks(long long V) { return (int)((V + P1_CHUNK - 1) / P1_CHUNK); }
-
 struct Scratch {
     float2* ms;
     float* cand_x;
@@ -336,14 +254,13 @@ struct Scratch {
 };
 Scratch carve(int B, int K, long long V, char* base) {
     const size_t rows = (size_t)B * K, nc = n_chunks(V), R = 2 * (size_t)K;
+    Carve c{base};
     Scratch s;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* r = base ? base + off : nullptr; off += align256(bytes); return r; };
-    s.ms = (float2*)take(rows * nc * sizeof(float2));
-    s.cand_x = (float*)take(rows * nc * R * sizeof(float));
-    s.cand_i = (int*)take(rows * nc * R * sizeof(int));
-    s.keys = (unsigned long long*)take(rows * nc * R * sizeof(unsigned long long));
-    s.total = off;
+    s.ms = c.take<float2>(rows * nc * sizeof(float2));
+    s.cand_x = c.take<float>(rows * nc * R * sizeof(float));
+    s.cand_i = c.take<int>(rows * nc * R * sizeof(int));
+    s.keys = c.take<unsigned long long>(rows * nc * R * sizeof(unsigned long long));
+    s.total = c.total;
     return s;
 }
 
@@ -375,9 +292,7 @@ extern "C" int pk_beam_select(const void* logits, long long ld, long long V, int
     P1Args a1{logits, ld, (int)V, K, hyp_in == nullptr, nc, forced, pad, eos, blacklist, n_blacklist, s.ms, s.cand_x, s.cand_i};
     const dim3 grid1((unsigned)((nc + P1_WAVES - 1) / P1_WAVES), (unsigned)(B * K));
     PK_DTYPE_SWITCH(dtype, "pk_beam_select", {
-        // 16-byte loads need every row to start on a 16-byte boundary; anything else is read element by element
-        const bool aligned = ((uintptr_t)logits % 16 == 0) && ((ld * (long long)sizeof(T)) % 16 == 0);
-        if (aligned) hipLaunchKernelGGL((beam_pass1_kernel<T, true>), grid1, dim3(64 * P1_WAVES), 0, st, a1);
+        if (rows_aligned16(logits, ld, sizeof(T))) hipLaunchKernelGGL((beam_pass1_kernel<T, true>), grid1, dim3(64 * P1_WAVES), 0, st, a1);
         else hipLaunchKernelGGL((beam_pass1_kernel<T, false>), grid1, dim3(64 * P1_WAVES), 0, st, a1);
     })
     PK_LAUNCH_CHECK();

@@ -50,6 +50,19 @@ extern "C" void pk_set_error(const char* fmt, ...);
         }                                                                        \
     } while (0)
 
+// ---- host: a caller's scratch buffer, cut into 256-byte aligned pieces in the order they are taken.  Without a base
+// (the *_scratch size queries) every piece is null and `total` is the size a real buffer needs ----
+inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+struct Carve {
+    char* base;
+    size_t total = 0;
+    template <typename P = char> P* take(size_t bytes) {
+        char* r = base ? base + total : nullptr;
+        total += align256(bytes);
+        return (P*)r;
+    }
+};
+
 __device__ __forceinline__ float bf2f(unsigned short u) { return __uint_as_float(((unsigned)u) << 16); }
 // round-to-nearest-even f32 -> bf16 through the compiler's cast (keeps NaN a NaN, v_cvt_pk_bf16_f32 at -O3)
 __device__ __forceinline__ unsigned short f2bf(float f) {

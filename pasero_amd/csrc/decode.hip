@@ -116,8 +116,6 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const T* __restrict__ 
     if (threadIdx.x == 0) out[row * out_stride] = si[0] < n ? si[0] : 0;
 }
 
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
 struct Scratch {
     char *x0, *x1, *h, *qkv, *q, *o, *ff, *ad;
     float *lse, *mean, *rstd;
@@ -127,26 +125,25 @@ struct Scratch {
 Scratch carve(const PkDecoderPlan* p, int B, char* base, const PkAdapterStack* adapters) {
     const size_t es = p->dtype == PK_F32 ? 4 : 2;
     Scratch s;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* r = base ? base + off : nullptr; off += align256(bytes); return r; };
-    s.x0 = take((size_t)B * p->d * es);
-    s.x1 = take((size_t)B * p->d * es);
-    s.h = take((size_t)B * p->d * es);
-    s.qkv = take((size_t)B * 3 * p->d * es);
-    s.q = take((size_t)B * p->d * es);
-    s.o = take((size_t)B * p->d * es);
-    s.ff = take((size_t)B * p->ffn * es);
-    s.lse = (float*)take((size_t)B * p->heads * 4);
-    s.mean = (float*)take((size_t)B * 4);
-    s.rstd = (float*)take((size_t)B * 4);
+    Carve c{base};
+    s.x0 = c.take((size_t)B * p->d * es);
+    s.x1 = c.take((size_t)B * p->d * es);
+    s.h = c.take((size_t)B * p->d * es);
+    s.qkv = c.take((size_t)B * 3 * p->d * es);
+    s.q = c.take((size_t)B * p->d * es);
+    s.o = c.take((size_t)B * p->d * es);
+    s.ff = c.take((size_t)B * p->ffn * es);
+    s.lse = c.take<float>((size_t)B * p->heads * 4);
+    s.mean = c.take<float>((size_t)B * 4);
+    s.rstd = c.take<float>((size_t)B * 4);
     s.ad_bytes = 0;
     for (int l = 0; adapters && l < p->n_layers; ++l)
         for (int i = 0; i < adapters[l].n && i < PK_ADAPTER_STACK_MAX; ++i) {
             const size_t need = pk_adapter_rows_step_scratch(B, p->d, adapters[l].a[i].p, p->dtype);
             if (need > s.ad_bytes) s.ad_bytes = need;
         }
-    s.ad = take(s.ad_bytes);
-    s.total = off;
+    s.ad = c.take(s.ad_bytes);
+    s.total = c.total;
     return s;
 }
 

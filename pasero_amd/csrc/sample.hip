@@ -4,9 +4,9 @@
 // `.float().log_softmax(-1)`, the blacklist loop, the finished-row masked_fill_, and `argmax`, or `topk` + `exp` +
 // `multinomial`, or `exp` + full descending `sort` + `cumsum` + mask + `multinomial`, and the forced prompt token.
 //
-//   pass 1  grid (chunks of V, rows), one WAVE per (row, chunk of 2048), as beam.hip's pass 1: 16-byte loads straight to
-//           registers, repeat penalty (rounded to the logits' dtype), temperature; the chunk's (max, sum exp) and its best
-//           live logit (for the greedy mode).
+//   pass 1  grid (chunks of V, rows), one WAVE per (row, chunk of 2048): the row scan of vocab_scan.h (chunk loader,
+//           slot mapping, the chunk's (max, sum exp)) under the repeat penalty (rounded to the logits' dtype) and the
+//           temperature; and the chunk's best live logit (for the greedy mode).
 //   pass 2  one workgroup per row.  Folds the chunks into the row's log-sum-exp (fixed order, fp64).  greedy: the best of
 //           the chunks' bests.  Otherwise NO sort: "first token, in the order (probability descending, id ascending),
 //           whose inclusive cumulative weight exceeds a target" is a radix select over the 64-bit key
@@ -20,34 +20,18 @@
 // integer addition is associative, so every sum is independent of arrival order (two calls on the same inputs give the
 // same bits) and carries no accumulation error at all — the only error left is expf's and the log-sum-exp's.
 // Both launches are ordinary launches on the caller's stream; no global atomics, no inter-workgroup hand-off.
-#include <math.h>
-#include "common.h"
+#include "vocab_scan.h"
 
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr int S_E = 32;                // logits per lane
-constexpr int S_CHUNK = 64 * S_E;      // logits per wave
 constexpr int S1_WAVES = 4;            // pass 1: waves (= chunks) per workgroup
 constexpr int S2_THREADS = 1024;
 constexpr int S2_WAVES = S2_THREADS / 64;
 constexpr int S_CAP = 1024;            // keys ranked exactly in LDS: one per thread
 constexpr float FIX_ONE = 4611686018427387904.0f;  // 2^62
 enum { MODE_GREEDY = 0, MODE_TOPK = 1, MODE_TOPP = 2, MODE_FULL = 3 };
-
-__device__ __forceinline__ unsigned ordered_bits(float f) {
-    unsigned u = __float_as_uint(f + 0.0f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ u64 wave_max_u64(u64 k) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        u64 o = __shfl_xor(k, off, 64);
-        k = o > k ? o : k;
-    }
-    return k;
-}
 
 struct SArgs {
     const void* logits;
@@ -80,36 +64,13 @@ template <typename T> __device__ __forceinline__ float penalised(float x, float 
     return to_f32(from_f32<T>(x < 0.f ? x * penalty : x / penalty));  // the reference works in the logits' dtype
 }
 
-// The (row, chunk)'s logits after repeat penalty and temperature; slot s = j * EPV + e of a lane holds token
-// base + (j * 64 + lane) * EPV + e.  `dead`: bit s set = out of the row, blacklisted, or not `pad` on a finished row.
+// The (row, chunk)'s logits after repeat penalty and temperature, in vocab_scan.h's slots.  `dead`: bit s set = out of
+// the row, blacklisted, or not `pad` on a finished row.
 template <typename T, bool ALIGNED>
-__device__ __forceinline__ void load_chunk(const SArgs& a, int row, int chunk, int lane, float (&v)[S_E], unsigned& dead) {
-    constexpr int EPV = 16 / sizeof(T);
-    constexpr int NL = S_E / EPV;
-    const T* p = (const T*)a.logits + (long long)row * a.ld;
-    const int base = chunk * S_CHUNK;
-    const int lim = a.V - base < S_CHUNK ? a.V - base : S_CHUNK;  // live tokens of the chunk
-    dead = 0;
-#pragma unroll
-    for (int j = 0; j < NL; ++j) {
-        const int i0 = base + (j * 64 + lane) * EPV;
-        if constexpr (ALIGNED) {
-            if (i0 + EPV <= a.V) {
-                Vec16<T> q = load16<T>(p + i0);
-#pragma unroll
-                for (int e = 0; e < EPV; ++e) v[j * EPV + e] = q.get(e) + 0.0f;
-            } else {  // the row's tail (and what lies behind it): nothing past element V - 1 is read
-#pragma unroll
-                for (int e = 0; e < EPV; ++e) v[j * EPV + e] = (i0 + e < a.V) ? to_f32(p[i0 + e]) + 0.0f : -INFINITY;
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < EPV; ++e) v[j * EPV + e] = (i0 + e < a.V) ? to_f32(p[i0 + e]) + 0.0f : -INFINITY;
-        }
-#pragma unroll
-        for (int e = 0; e < EPV; ++e)
-            if (i0 + e >= a.V) dead |= 1u << (j * EPV + e);
-    }
+__device__ __forceinline__ void masked_chunk(const SArgs& a, int row, int chunk, int lane, float (&v)[SCAN_E], unsigned& dead) {
+    const int base = chunk * SCAN_CHUNK;
+    const int lim = a.V - base < SCAN_CHUNK ? a.V - base : SCAN_CHUNK;  // live tokens of the chunk
+    load_chunk<T, ALIGNED>((const T*)a.logits + (long long)row * a.ld, a.V, base, lane, v, dead);
     if (a.n_hist > 0 && a.penalty != 1.0f) {
         unsigned pen = 0;  // a token that occurs twice in the history is penalised once
         const long long* h = a.hist + (long long)row * a.hist_ld;
@@ -120,34 +81,26 @@ __device__ __forceinline__ void load_chunk(const SArgs& a, int row, int chunk, i
             while (hits) {
                 const int src = __ffsll((long long)hits) - 1;
                 hits &= hits - 1;
-                const int r = __shfl(rel, src, 64);
-                if (lane == (r / EPV) % 64) pen |= 1u << ((r / (64 * EPV)) * EPV + r % EPV);
+                pen |= slot_bit<T>(__shfl(rel, src, 64), lane);
             }
         }
 #pragma unroll
-        for (int s = 0; s < S_E; ++s)
+        for (int s = 0; s < SCAN_E; ++s)
             if ((pen >> s) & 1u) v[s] = penalised<T>(v[s], a.penalty);
     }
     if (a.inv_temp != 1.0f) {
 #pragma unroll
-        for (int s = 0; s < S_E; ++s) v[s] *= a.inv_temp;
+        for (int s = 0; s < SCAN_E; ++s) v[s] *= a.inv_temp;
     }
     for (int b = 0; b < a.n_black; ++b) {
         const long long id = a.blacklist[b];
         if (id < base || id >= (long long)base + lim) continue;  // wave-uniform
-        const int r = (int)(id - base);
-        if (lane == (r / EPV) % 64) dead |= 1u << ((r / (64 * EPV)) * EPV + r % EPV);
+        dead |= slot_bit<T>((int)(id - base), lane);
     }
     if (a.finished && a.finished[row]) {
-        unsigned keep = 0;
         const long long r = a.pad - base;
-        if (r >= 0 && r < lim && lane == (int)(r / EPV) % 64) keep = 1u << (((int)r / (64 * EPV)) * EPV + (int)r % EPV);
-        dead |= ~keep;
+        dead |= ~(r >= 0 && r < lim ? slot_bit<T>((int)r, lane) : 0u);
     }
-}
-template <typename T> __device__ __forceinline__ int slot_token(int base, int lane, int s) {
-    constexpr int EPV = 16 / sizeof(T);
-    return base + ((s / EPV) * 64 + lane) * EPV + (s % EPV);
 }
 
 template <typename T, bool ALIGNED>
@@ -156,38 +109,23 @@ __global__ __launch_bounds__(64 * S1_WAVES) void sample_pass1_kernel(SArgs a) {
     const int chunk = blockIdx.x * S1_WAVES + (threadIdx.x >> 6);
     const int row = blockIdx.y;
     if (chunk >= a.nchunks) return;  // wave-uniform
-    float v[S_E];
+    float v[SCAN_E];
     unsigned dead;
-    load_chunk<T, ALIGNED>(a, row, chunk, lane, v, dead);
+    masked_chunk<T, ALIGNED>(a, row, chunk, lane, v, dead);
     // the normaliser covers the whole row: masked tokens do not leave it
-    float m = -INFINITY;
-#pragma unroll
-    for (int s = 0; s < S_E; ++s) m = fmaxf(m, v[s]);
-    float sum = 0.f;
-    if (m != -INFINITY) {
-#pragma unroll
-        for (int s = 0; s < S_E; ++s) sum += expf(v[s] - m);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float m2 = __shfl_xor(m, off, 64), s2 = __shfl_xor(sum, off, 64);
-        const float M = fmaxf(m, m2);
-        const float f1 = (m == -INFINITY) ? 0.f : expf(m - M), f2 = (m2 == -INFINITY) ? 0.f : expf(m2 - M);
-        sum = sum * f1 + s2 * f2;
-        m = M;
-    }
+    const float2 ms = chunk_max_sum(v);
     u64 key = 0;
-    const int base = chunk * S_CHUNK;
+    const int base = chunk * SCAN_CHUNK;
 #pragma unroll
-    for (int s = 0; s < S_E; ++s) {
+    for (int s = 0; s < SCAN_E; ++s) {
         if (!((dead >> s) & 1u) && v[s] > -INFINITY) {
-            const u64 k = ((u64)ordered_bits(v[s]) << 32) | (u64)(0xffffffffu - (unsigned)slot_token<T>(base, lane, s));
+            const u64 k = rank_key(v[s], (unsigned)slot_token<T>(base, lane, s));
             key = k > key ? k : key;
         }
     }
     key = wave_max_u64(key);
     if (lane == 0) {
-        a.ms[(long long)row * a.nchunks + chunk] = make_float2(m, sum);
+        a.ms[(long long)row * a.nchunks + chunk] = ms;
         a.best[(long long)row * a.nchunks + chunk] = key;
     }
 }
@@ -263,21 +201,10 @@ __global__ __launch_bounds__(S2_THREADS) void sample_pass2_kernel(SArgs a) {
 
     // ---- the row's log-sum-exp from its chunks, in a fixed order ----
     if (wave == 0) {
-        const float2* ms = a.ms + (long long)row * a.nchunks;
-        float M = -INFINITY;
-        for (int c = lane; c < a.nchunks; c += 64) M = fmaxf(M, ms[c].x);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) M = fmaxf(M, __shfl_xor(M, off, 64));
-        double S = 0.0;
-        for (int c = lane; c < a.nchunks; c += 64) {
-            const float2 e = ms[c];
-            if (e.x != -INFINITY) S += (double)e.y * exp((double)e.x - (double)M);
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) S += __shfl_xor(S, off, 64);
+        const float2 f = fold_chunks(a.ms + (long long)row * a.nchunks, a.nchunks, lane);
         if (lane == 0) {
-            s_max = M;
-            s_logsum = S > 0.0 ? (float)log(S) : 0.f;
+            s_max = f.x;
+            s_logsum = f.y;
         }
     }
     __syncthreads();
@@ -286,12 +213,12 @@ __global__ __launch_bounds__(S2_THREADS) void sample_pass2_kernel(SArgs a) {
     // f(d, id) on every live token with a finite logit; d = max - x >= 0
     auto sweep = [&](auto&& f) {
         for (int c = wave; c < a.nchunks; c += S2_WAVES) {
-            float v[S_E];
+            float v[SCAN_E];
             unsigned dead;
-            load_chunk<T, ALIGNED>(a, row, c, lane, v, dead);
+            masked_chunk<T, ALIGNED>(a, row, c, lane, v, dead);
 #pragma unroll
-            for (int s = 0; s < S_E; ++s)
-                if (!((dead >> s) & 1u) && v[s] > -INFINITY) f(m - v[s], slot_token<T>(c * S_CHUNK, lane, s));
+            for (int s = 0; s < SCAN_E; ++s)
+                if (!((dead >> s) & 1u) && v[s] > -INFINITY) f(m - v[s], slot_token<T>(c * SCAN_CHUNK, lane, s));
         }
     };
     auto fix = [&](float d) -> u64 { return __float2ull_rz(expf(-d - logsum) * FIX_ONE); };  // exp((x - max) - log(sum))
@@ -394,7 +321,7 @@ __global__ __launch_bounds__(S2_THREADS) void sample_pass2_kernel(SArgs a) {
         __syncthreads();
         if (tid == 0) {
             for (int i = 0; i < S2_WAVES; ++i) k = wave_best[i] > k ? wave_best[i] : k;
-            s_token = k ? (int)(0xffffffffu - (unsigned)k) : 0;  // nothing live: argmax of a row of -inf
+            s_token = k ? (int)key_index(k) : 0;  // nothing live: argmax of a row of -inf
         }
         __syncthreads();
     } else {
@@ -470,9 +397,6 @@ __global__ __launch_bounds__(S2_THREADS) void sample_pass2_kernel(SArgs a) {
     }
 }
 
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-inline int n_chunks(long long V) { return (int)((V + S_CHUNK - 1) / S_CHUNK); }
-
 }  // namespace
 
 extern "C" size_t pk_sample_select_scratch(int B, long long V) {
@@ -522,9 +446,7 @@ extern "C" int pk_sample_select(const void* logits, long long ld, long long V, i
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid1((unsigned)((nc + S1_WAVES - 1) / S1_WAVES), (unsigned)B);
     PK_DTYPE_SWITCH(dtype, "pk_sample_select", {
-        // 16-byte loads need every row to start on a 16-byte boundary; anything else is read element by element
-        const bool aligned = ((uintptr_t)logits % 16 == 0) && ((ld * (long long)sizeof(T)) % 16 == 0);
-        if (aligned) {
+        if (rows_aligned16(logits, ld, sizeof(T))) {
             hipLaunchKernelGGL((sample_pass1_kernel<T, true>), grid1, dim3(64 * S1_WAVES), 0, st, a);
             hipLaunchKernelGGL((sample_pass2_kernel<T, true>), dim3((unsigned)B), dim3(S2_THREADS), 0, st, a);
         } else {

@@ -326,6 +326,11 @@ class DecodeCache:
         self._publish(state)
         return logits[:, :self.V].unsqueeze(1)
 
+    def _gather_cross(self, idx: Tensor):
+        """select sentences of the cross-attention K|V and of the encoder mask"""
+        self.cross = [c.view(-1, self.S, 2 * self.D).index_select(0, idx).view(-1, 2 * self.D) for c in self.cross]
+        self.mask = None if self.mask is None else self.mask.index_select(0, idx)
+
     def reorder(self, indices: Tensor, state: dict):
         """beam search (transformer.py:68-75): select sentences / hypotheses along the batch dimension"""
         idx = indices.to(self.k[0].device)
@@ -333,8 +338,7 @@ class DecodeCache:
         self.v = [c[:self.B].index_select(0, idx) for c in self.v]
         self.B = idx.numel()
         self._spare = None
-        self.cross = [c.view(-1, self.S, 2 * self.D).index_select(0, idx).view(-1, 2 * self.D) for c in self.cross]
-        self.mask = None if self.mask is None else self.mask.index_select(0, idx)
+        self._gather_cross(idx)
         nbytes = self._scratch_bytes(self.B)
         if nbytes > self.scratch.numel():
             self.scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.scratch.device)
@@ -361,8 +365,7 @@ class DecodeCache:
         self._spare, self.k, self.v = (self.k, self.v), k2, v2
         self.B = rows_out
         if shrink:
-            self.cross = [c.view(-1, self.S, 2 * self.D).index_select(0, idx).view(-1, 2 * self.D) for c in self.cross]
-            self.mask = None if self.mask is None else self.mask.index_select(0, idx)
+            self._gather_cross(idx)
         self._tables()
         self._publish(state)
 
@@ -423,6 +426,26 @@ def try_step(decoder, encoder_out: Tensor, encoder_mask: Optional[Tensor], decod
     return logits
 
 
+def _select_operands(logits: Tensor, V: int, contiguous=(), strided=()):
+    """what BeamSelect.run and SampleSelect.run ask of their operands.  Returns the logits with unit column stride (a
+    contiguous copy if they had another) and their row pitch (one row: at least V); asserts of every (tensor | None,
+    dtype) pair that it has the dtype and lies on the device, and of the `contiguous` ones that they are contiguous"""
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    ld = logits.stride(0) if logits.size(0) > 1 else max(V, logits.stride(0))
+    for t, dt in contiguous:
+        assert t is None or (t.dtype == dt and t.is_contiguous() and t.is_cuda)
+    for t, dt in strided:
+        assert t is None or (t.dtype == dt and t.is_cuda)
+    return logits, ld
+
+
+def _prompt_logprobs(logits: Tensor, next_tokens: Tensor) -> Tensor:
+    """log-probabilities of a prompt's tokens under the first decoder call (decoding.py:1395-1402): logits (B, n + 1, V),
+    next_tokens (B, n) -> (B, n), plain torch"""
+    return logits[:, :-1].float().log_softmax(dim=-1).gather(2, next_tokens.unsqueeze(2)).squeeze(2)
+
+
 # ---- beam search (pasero/decoding.py:1225-1657) ----------------------------------------------------------------------
 class BeamSelect:
     """buffers of pk_beam_select for searches of up to B sentences x K beams over V tokens, and the call itself.
@@ -450,13 +473,10 @@ class BeamSelect:
         """logits (B*K, V), any row stride, fp32 / bf16 / fp16"""
         require_gpu(logits)
         assert logits.dim() == 2 and logits.size(0) == B * self.K and logits.size(1) == self.V and B <= self.B
-        if logits.stride(1) != 1:
-            logits = logits.contiguous()
-        ld = logits.stride(0) if logits.size(0) > 1 else max(self.V, logits.stride(0))
+        logits, ld = _select_operands(logits, self.V, contiguous=(
+            (hyp, torch.float32), (row_bias, torch.float32), (forced, torch.int64), (blacklist, torch.int64),
+            (eos_counts, torch.uint8)))
         out = self._scores[1] if (hyp is not None and hyp.data_ptr() == self._scores[0].data_ptr()) else self._scores[0]
-        for t, dt in ((hyp, torch.float32), (row_bias, torch.float32), (forced, torch.int64), (blacklist, torch.int64),
-                      (eos_counts, torch.uint8)):
-            assert t is None or (t.dtype == dt and t.is_contiguous() and t.is_cuda)
         check(lib.load().pk_beam_select(
             ptr(logits), ld, self.V, B, self.K, dtype_code(logits), ptr(hyp), ptr(row_bias), ptr(forced), int(pad), int(eos),
             ptr(blacklist), 0 if blacklist is None else blacklist.numel(), ptr(eos_counts), ptr(self.scratch),
@@ -492,6 +512,52 @@ def _uncollate(hyp: dict, padding_idx: int, src_mask: Optional[Tensor]):
             hyp[k] = v[~pad_at]
 
 
+def _single(decoder, encoder_outputs, encoder_masks, return_layers, sharded, who):
+    """the one decoder / encoder output / mask of a search, or NotImplementedError naming the option"""
+    if isinstance(encoder_outputs, (list, tuple)):
+        if len(encoder_outputs) > 1:
+            raise NotImplementedError(f'pasero_amd {who}: ensembles (several decoders) are not implemented')
+        encoder_outputs = encoder_outputs[0] if encoder_outputs else None
+    if isinstance(encoder_masks, (list, tuple)):
+        encoder_masks = encoder_masks[0] if encoder_masks else None
+    if len(getattr(decoder, 'decoders', ())) > 1:
+        raise NotImplementedError(f'pasero_amd {who}: ensembles (several decoders) are not implemented')
+    if return_layers:
+        raise NotImplementedError(f'pasero_amd {who}: return_layers is not implemented')
+    if sharded:
+        raise NotImplementedError(f'pasero_amd {who}: sharded=True is not implemented')
+    if encoder_outputs is None:
+        raise NotImplementedError(f'pasero_amd {who}: decoder-only models (empty encoder_outputs) are not implemented')
+    if getattr(decoder, 'decoders', None):  # a one-element ensemble wrapper
+        decoder = decoder.decoders[0]
+    return decoder, encoder_outputs, encoder_masks
+
+
+def _search_setup(decoder, encoder_outputs, encoder_masks, return_layers, sharded, who, device, decoder_input,
+                  max_output_len, blacklist):
+    """what both searches start with: the one decoder (in eval mode), the encoder output and mask on the device, B, pad,
+    eos, the prompt (`decoder_input`, BOS by default), its lengths `plen` (B,) with their minimum `lo` and maximum `hi`
+    (the set-up's one host read), the length limit `max_len` and the blacklist as a tensor (None when empty)"""
+    decoder, enc, enc_mask = _single(decoder, encoder_outputs, encoder_masks, return_layers, sharded, who)
+    decoder.eval()
+    dev = torch.device(device) if device is not None else enc.device
+    enc, enc_mask = enc.to(dev), None if enc_mask is None else enc_mask.to(dev)
+    require_gpu(enc)
+    B = enc.size(0)
+    if decoder_input is None:
+        decoder_input = torch.full((B, 1), decoder.bos_idx, dtype=torch.long, device=dev)
+    decoder_input = decoder_input.to(dev)
+    assert decoder_input.dim() == 2 and decoder_input.size(0) == B
+    not_pad = decoder_input != decoder.padding_idx
+    plen = (not_pad * torch.arange(1, decoder_input.size(1) + 1, device=dev)).amax(dim=1)  # utils.mask_to_len
+    lo, hi = (int(x) for x in torch.stack([plen.min(), plen.max()]).tolist())  # (before the loop: not a step's read)
+    assert lo > 0
+    max_len = min(decoder.max_len, hi + max_output_len)
+    assert max_len >= 1
+    black = torch.tensor(list(blacklist), dtype=torch.int64, device=dev) if len(blacklist) else None
+    return decoder, enc, enc_mask, B, decoder.padding_idx, decoder.eos_idx, decoder_input, plen, lo, hi, max_len, black
+
+
 def beam_search(decoder, encoder_outputs, encoder_masks, max_output_len: int, beam_size: int, meta: dict, *,
                 return_scores: bool = False, decoder_input: Optional[Tensor] = None, return_layers=[],
                 sharded: bool = False, enc_layer_outputs: dict = {}, device=None, len_penalty: float = 1.0,
@@ -513,39 +579,10 @@ def beam_search(decoder, encoder_outputs, encoder_masks, max_output_len: int, be
     if kwargs.get('repeat_penalty', 1.0) != 1.0 and not _warned_repeat_penalty:
         _warned_repeat_penalty = True
         warnings.warn("'repeat_penalty' is not supported in beam search")
-    if isinstance(encoder_outputs, (list, tuple)):
-        if len(encoder_outputs) > 1:
-            raise NotImplementedError('pasero_amd beam_search: ensembles (several decoders) are not implemented')
-        encoder_outputs = encoder_outputs[0] if encoder_outputs else None
-    if isinstance(encoder_masks, (list, tuple)):
-        encoder_masks = encoder_masks[0] if encoder_masks else None
-    if len(getattr(decoder, 'decoders', ())) > 1:
-        raise NotImplementedError('pasero_amd beam_search: ensembles (several decoders) are not implemented')
-    if return_layers:
-        raise NotImplementedError('pasero_amd beam_search: return_layers is not implemented')
-    if sharded:
-        raise NotImplementedError('pasero_amd beam_search: sharded=True is not implemented')
-    if encoder_outputs is None:
-        raise NotImplementedError('pasero_amd beam_search: decoder-only models (empty encoder_outputs) are not implemented')
-    for d in getattr(decoder, 'decoders', ()):
-        decoder = d
-    decoder.eval()
-    K = int(beam_size)
-    dev = torch.device(device) if device is not None else encoder_outputs.device
-    enc, enc_mask = encoder_outputs.to(dev), None if encoder_masks is None else encoder_masks.to(dev)
-    require_gpu(enc)
-    B0 = enc.size(0)
-    pad, eos = decoder.padding_idx, decoder.eos_idx
-    if decoder_input is None:
-        decoder_input = torch.full((B0, 1), decoder.bos_idx, dtype=torch.long, device=dev)
-    decoder_input = decoder_input.to(dev)
-    assert decoder_input.dim() == 2 and decoder_input.size(0) == B0
-    not_pad = decoder_input != pad
-    plen = (not_pad * torch.arange(1, decoder_input.size(1) + 1, device=dev)).amax(dim=1)  # utils.mask_to_len
-    lo, hi = (int(x) for x in torch.stack([plen.min(), plen.max()]).tolist())
-    assert lo > 0
-    max_len = min(decoder.max_len, hi + max_output_len)
-    assert max_len >= 1
+    decoder, enc, enc_mask, B0, pad, eos, decoder_input, plen, lo, hi, max_len, black = _search_setup(
+        decoder, encoder_outputs, encoder_masks, return_layers, sharded, 'beam_search', device, decoder_input,
+        max_output_len, blacklist)
+    K, dev = int(beam_size), enc.device
     tokens = torch.full((B0 * K, max_len), eos, dtype=torch.long, device=dev)  # EOS as filler: a hypothesis ends with it
     width = min(decoder_input.size(1), max_len)
     tokens[:, :width] = decoder_input.repeat_interleave(K, dim=0)[:, :width]
@@ -554,7 +591,6 @@ def beam_search(decoder, encoder_outputs, encoder_masks, max_output_len: int, be
     enc = enc.repeat_interleave(K, dim=0)
     enc_mask = None if enc_mask is None else enc_mask.repeat_interleave(K, dim=0)
     cum = torch.zeros(B0 * K, max_len, dtype=torch.float32, device=dev) if return_scores else None
-    black = torch.tensor(list(blacklist), dtype=torch.int64, device=dev) if len(blacklist) else None
     select = None
     finished = [[] for _ in range(B0)]
     alive = list(range(B0))      # current batch index -> initial batch index
@@ -569,8 +605,7 @@ def beam_search(decoder, encoder_outputs, encoder_masks, max_output_len: int, be
             if logits.size(1) > 1:  # the first call carries the prompt: score its tokens (decoding.py:1395-1402)
                 assert step == lo
                 nxt = feed[:, 1:]
-                prompt_scores = logits[:, :-1].float().log_softmax(dim=-1).gather(2, nxt.unsqueeze(2)).squeeze(2)
-                prompt_scores = prompt_scores * (nxt != pad)
+                prompt_scores = _prompt_logprobs(logits, nxt) * (nxt != pad)
                 bias = prompt_scores.sum(dim=1).contiguous()
             forced = tokens[:, step].contiguous() if step < hi else None
             counts = (plen_alive <= step).to(torch.uint8) if step < hi else None  # an EOS inside a prompt is no end
@@ -678,14 +713,9 @@ class SampleSelect:
         require_gpu(logits)
         B = logits.size(0)
         assert logits.dim() == 2 and logits.size(1) == self.V and B <= self.B
-        if logits.stride(1) != 1:
-            logits = logits.contiguous()
-        ld = logits.stride(0) if B > 1 else max(self.V, logits.stride(0))
-        for t, dt in ((history, torch.int64), (blacklist, torch.int64), (finished, torch.uint8), (uniforms, torch.float32),
-                      (forced, torch.int64), (out, torch.int64)):
-            assert t is None or (t.dtype == dt and t.is_cuda)
-        for t in (blacklist, finished, uniforms):
-            assert t is None or t.is_contiguous()
+        logits, ld = _select_operands(
+            logits, self.V, contiguous=((blacklist, torch.int64), (finished, torch.uint8), (uniforms, torch.float32)),
+            strided=((history, torch.int64), (forced, torch.int64), (out, torch.int64)))
         n_hist = hist_ld = 0
         if history is not None and history.size(1) > 0:
             assert history.dim() == 2 and history.size(0) == B and history.stride(1) == 1
@@ -706,27 +736,6 @@ class SampleSelect:
             'pk_sample_select')
 
 
-def _single(decoder, encoder_outputs, encoder_masks, return_layers, sharded, who):
-    """the one decoder / encoder output / mask of a search, or NotImplementedError naming the option"""
-    if isinstance(encoder_outputs, (list, tuple)):
-        if len(encoder_outputs) > 1:
-            raise NotImplementedError(f'pasero_amd {who}: ensembles (several decoders) are not implemented')
-        encoder_outputs = encoder_outputs[0] if encoder_outputs else None
-    if isinstance(encoder_masks, (list, tuple)):
-        encoder_masks = encoder_masks[0] if encoder_masks else None
-    if len(getattr(decoder, 'decoders', ())) > 1:
-        raise NotImplementedError(f'pasero_amd {who}: ensembles (several decoders) are not implemented')
-    if return_layers:
-        raise NotImplementedError(f'pasero_amd {who}: return_layers is not implemented')
-    if sharded:
-        raise NotImplementedError(f'pasero_amd {who}: sharded=True is not implemented')
-    if encoder_outputs is None:
-        raise NotImplementedError(f'pasero_amd {who}: decoder-only models (empty encoder_outputs) are not implemented')
-    if getattr(decoder, 'decoders', None):  # a one-element ensemble wrapper
-        decoder = decoder.decoders[0]
-    return decoder, encoder_outputs, encoder_masks
-
-
 def sample_on_the_fly(decoder, encoder_outputs, encoder_masks, max_output_len: int, meta: dict, *,
                       return_scores: bool = False, decoder_input: Optional[Tensor] = None,
                       sampling_temperature: float = 1.0, sampling_topk: int = 0, sampling_topp: float = 1.0,
@@ -744,27 +753,14 @@ def sample_on_the_fly(decoder, encoder_outputs, encoder_masks, max_output_len: i
     Not implemented (raise, naming the option): ensembles, `return_layers`, `sharded`, decoder-only models."""
     from . import rng
     assert sampling_topk == 0 or sampling_topp == 1, 'combining nucleus sampling and top-k sampling is not allowed'
-    decoder, enc, enc_mask = _single(decoder, encoder_outputs, encoder_masks, return_layers, sharded, 'sample_on_the_fly')
-    decoder.eval()
-    dev = torch.device(device) if device is not None else enc.device
-    enc, enc_mask = enc.to(dev), None if enc_mask is None else enc_mask.to(dev)
-    require_gpu(enc)
-    B = enc.size(0)
-    pad, eos = decoder.padding_idx, decoder.eos_idx
-    if decoder_input is None:
-        decoder_input = torch.full((B, 1), decoder.bos_idx, dtype=torch.long, device=dev)
-    decoder_input = decoder_input.to(dev)
-    assert decoder_input.dim() == 2 and decoder_input.size(0) == B
-    plen = ((decoder_input != pad) * torch.arange(1, decoder_input.size(1) + 1, device=dev)).amax(dim=1)  # utils.mask_to_len
-    lo, hi = (int(x) for x in torch.stack([plen.min(), plen.max()]).tolist())  # (before the loop: not a step's read)
-    assert lo > 0
-    max_len = min(decoder.max_len, hi + max_output_len)
-    assert max_len >= 1
+    decoder, enc, enc_mask, B, pad, eos, decoder_input, plen, lo, hi, max_len, black = _search_setup(
+        decoder, encoder_outputs, encoder_masks, return_layers, sharded, 'sample_on_the_fly', device, decoder_input,
+        max_output_len, blacklist)
+    dev = enc.device
     start = min(lo, max_len - 1)
     tokens = torch.full((B, max_len), pad, dtype=torch.long, device=dev)
     tokens[:, :decoder_input.size(1)] = decoder_input
     stops = [s.to(dev) for s in stop_sequences if len(s) > 0] + [torch.tensor([eos], dtype=torch.long, device=dev)]
-    black = torch.tensor(list(blacklist), dtype=torch.int64, device=dev) if len(blacklist) else None
     limit = plen + max_output_len
     has_eos = torch.zeros(B, dtype=torch.bool, device=dev)
     if sampling_temperature == 0 or sampling_topk == 1:
@@ -796,8 +792,7 @@ def sample_on_the_fly(decoder, encoder_outputs, encoder_masks, max_output_len: i
                 last = -select.logprob[:B].clone().unsqueeze(1)
                 if logits.size(1) > 1:  # the first call carries the prompt: score its tokens with plain torch
                     nxt = tokens[:, prev + 1:step]
-                    lp = logits[:, :-1].float().log_softmax(dim=-1).gather(2, nxt.unsqueeze(2)).squeeze(2)
-                    last = torch.cat([-lp, last], dim=1)
+                    last = torch.cat([-_prompt_logprobs(logits, nxt), last], dim=1)
                 out['pos_scores'] = last
             yield out
             # the stop test (decoding.py:1208-1212) on the device; one host read: the all-finished flag

@@ -21,6 +21,12 @@ for _i, _variant in enumerate(('first', 'forced', 'blacklist', 'sparse', 'eos_in
     for _dtype, _V, _K, _B in (('f32', 1003, 5, 4), ('bf16', 8032, 3, 4), ('f16', 70376, 5, 4), ('bf16', 61, 16, 4)):
         _seed += 1
         SELECT_CASES.append(_case(_dtype, _V, _K, _B, _variant, _seed))
+# rows that end exactly at, one past and one short of a 2048-token chunk (appended: the seeds above stay what they were)
+for _dtype in ('f32', 'bf16', 'f16'):
+    for _V, _K, _B in ((2048, 16, 4), (2049, 5, 4), (4096, 3, 4), (2047, 16, 1)):
+        for _variant in ('plain', 'blacklist', 'forced'):
+            _seed += 1
+            SELECT_CASES.append(_case(_dtype, _V, _K, _B, _variant, _seed))
 
 
 def case_id(c):

@@ -31,6 +31,14 @@ for _dtype in ('f32', 'bf16', 'f16'):
             _seed += 1
             SAMPLE_CASES.append(dict(dtype=_dtype, V=_V, B=_B, mode=_mode, variant='plain', seed=_seed))
 
+# rows that end exactly at and one past a 2048-token chunk, and two full chunks (appended, as above)
+for _dtype in ('f32', 'bf16', 'f16'):
+    for _V, _B in ((2048, 7), (2049, 7), (4096, 7)):
+        for _mode in MODES:
+            for _variant in ('plain', 'blacklist', 'penalty', 'finished'):
+                _seed += 1
+                SAMPLE_CASES.append(dict(dtype=_dtype, V=_V, B=_B, mode=_mode, variant=_variant, seed=_seed))
+
 
 def case_id(c):
     return f"{c['dtype']}-V{c['V']}-B{c['B']}-{c['mode']}-{c['variant']}"
