@@ -664,6 +664,55 @@ int pk_moe_gemm_wgrad(const void* dY, const void* X, void* const* dW, void* cons
                       int E, long long M, long long N, int dtype, void* stream);
 int pk_moe_use_grouped(int on);
 
+/* ---- Mixture of experts on few rows (csrc/moe_rows.hip): the inference form of MixtureOfExperts.forward
+ * (pasero/models/mixture_of_experts.py:141-190) — no padding mask, no load-balancing outputs — what a decoding step of
+ * `moe_transformer` runs in place of a layer's feed-forward block.
+ * pk_moerows_route: ONE launch of one workgroup for gate logits [rows][E] in the model's dtype (rows <= PK_MOE_ROWS_MAX):
+ *   fp32 softmax, top-2 (higher value first, the lower expert index among equal values), weights normalised to sum 1 and
+ *   the routing tables by a stable counting sort (expert, then token, then k).  top_idx, top_w, offsets, slot_of and
+ *   token_of[0 .. 2 rows) are bit for bit what pk_moe_gate writes for the same logits as fp32 without a padding mask;
+ *   entries of token_of beyond are not written.
+ * pk_moerows: y[rows][D] = sum_k top_w_k * expert_k(x), expert_e(x) = act(x w1_e^T + b1_e) w2_e^T + b2_e, the gate logits
+ *   being x gate_w^T (gate_w [E][D]) computed by pk_gemm in the model's dtype.  w1 / b1 / w2 / b2: device arrays of E device
+ *   pointers as pk_moe_gemm takes them (w1_e [F][D], w2_e [D][F]; b1 / b2 may be NULL).  y must not overlap x.  Rows >=
+ *   `rows` are untouched.  No allocation, no synchronisation; every argument is checked before any launch.
+ *   The few route (pk_moerows_few returns 1: 16-bit dtype, rows <= the threshold, D % 64 == 0, F % 64 == 0) is 5 launches:
+ *   gate GEMM, pk_moerows_route, fc1 addressed through token_of (no gather), fc2, pk_moe_combine; the two GEMMs walk an
+ *   expert's slots in chunks of 16 on v_mfma_f32_16x16x32 with K split over the waves, and an expert without slots costs a
+ *   workgroup that exits at once.  The grouped route (fp32, more rows, other sizes) runs the conversion of the logits to
+ *   fp32, pk_moe_gate, pk_moe_gather, pk_moe_gemm twice and pk_moe_combine inside the same call through `scratch`: bitwise
+ *   what the module computes.
+ * pk_moerows_few_max: sets (rows >= 0) or only asks for (rows < 0) the row threshold of the few route; returns the previous
+ *   one.  Initial value 256 (the rule of the dense few-rows GEMM; env PK_MOE_ROWS_FEW_MAX overrides it at library load).
+ * pk_moerows_scratch: bytes of `scratch` pk_moerows needs on either route; 0 for sizes the call refuses. */
+#define PK_MOE_ROWS_MAX 1024
+int pk_moerows_route(const void* logits, long long rows, int E, int dtype, int* top_idx, float* top_w, int* offsets,
+                      int* slot_of, int* token_of, void* stream);
+int pk_moerows_few(long long rows, int E, int D, int F, int dtype);
+int pk_moerows_few_max(int rows);
+size_t pk_moerows_scratch(long long rows, int E, int D, int F, int dtype);
+int pk_moerows(const void* x, void* y, const void* gate_w, const void* const* w1, const void* const* b1,
+                const void* const* w2, const void* const* b2, long long rows, int E, int D, int F, int act, int dtype,
+                void* scratch, size_t scratch_bytes, void* stream);
+
+/* pk_decoder_step for decoders with mixture-of-experts layers (`moe_transformer`).  `moe`: a host array of plan->n_layers
+ * entries (E == 0: a dense layer), or NULL — then the call IS pk_decoder_step_ex, launch for launch.  In a layer with E > 0
+ * the feed-forward block's two projections are ONE pk_moerows call on the block's input (x for post-norm, LN(x) for
+ * pre-norm) with the plan's activation; the block end is unchanged; fc1_* / fc2_* of that layer are not read. */
+typedef struct {
+    int E, F;
+    const void* gate_w;
+    const void* const* w1;   /* device arrays of E device pointers, as pk_moe_gemm takes them; b1 / b2 may be NULL */
+    const void* const* b1;
+    const void* const* w2;
+    const void* const* b2;
+} PkMoeLayer;
+size_t pk_decoder_step_scratch_moe(const PkDecoderPlan* plan, int B, const PkAdapterStack* adapters, const PkMoeLayer* moe);
+int pk_decoder_step_moe(const PkDecoderPlan* plan, const long long* ids, int B, int t, int pos_start, void* const* self_k,
+                        void* const* self_v, long long cap, const void* const* cross_kv, const unsigned char* enc_mask,
+                        int S, void* scratch, size_t scratch_bytes, void* logits, long long ld_logits,
+                        const PkAdapterStack* adapters, const PkMoeLayer* moe, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

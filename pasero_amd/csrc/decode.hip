@@ -32,6 +32,10 @@ size_t pk_adapter_rows_step_scratch(long long rows, int d, int p, int dtype);
 int pk_adapter_rows_step(const void* x, void* y, const void* ln_g, const void* ln_b, const void* down_w, const void* down_b,
                     const void* up_w, const void* up_b, long long rows, int d, int p, int act, float scaling, float eps,
                     int dtype, void* scratch, size_t scratch_bytes, void* stream);
+size_t pk_moerows_scratch(long long rows, int E, int D, int F, int dtype);
+int pk_moerows(const void* x, void* y, const void* gate_w, const void* const* w1, const void* const* b1,
+                const void* const* w2, const void* const* b2, long long rows, int E, int D, int F, int act, int dtype,
+                void* scratch, size_t scratch_bytes, void* stream);
 }
 
 // ---- plan: mirrors include/pasero_hip.h (PkDecoderLayerWeights / PkDecoderPlan) ----
@@ -69,6 +73,15 @@ struct PkAdapter {
 struct PkAdapterStack {
     int n;
     PkAdapter a[PK_ADAPTER_STACK_MAX];
+};
+// a layer whose feed-forward block is a mixture of experts (E == 0: a dense layer)
+struct PkMoeLayer {
+    int E, F;
+    const void* gate_w;
+    const void* const* w1;   /* device arrays of E device pointers, as pk_moe_gemm takes them; b1 / b2 may be NULL */
+    const void* const* b1;
+    const void* const* w2;
+    const void* const* b2;
 };
 
 namespace {
@@ -117,12 +130,13 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const T* __restrict__ 
 }
 
 struct Scratch {
-    char *x0, *x1, *h, *qkv, *q, *o, *ff, *ad;
+    char *x0, *x1, *h, *qkv, *q, *o, *ff, *ad, *moe;
     float *lse, *mean, *rstd;
-    size_t total, ad_bytes;
+    size_t total, ad_bytes, moe_bytes;
 };
-// `adapters` adds, behind everything else, the largest three-launch scratch one of them needs
-Scratch carve(const PkDecoderPlan* p, int B, char* base, const PkAdapterStack* adapters) {
+// `adapters` adds, behind everything else, the largest three-launch scratch one of them needs; `moe`, behind that, the
+// largest pk_moerows scratch among the layers
+Scratch carve(const PkDecoderPlan* p, int B, char* base, const PkAdapterStack* adapters, const PkMoeLayer* moe) {
     const size_t es = p->dtype == PK_F32 ? 4 : 2;
     Scratch s;
     Carve c{base};
@@ -143,14 +157,25 @@ Scratch carve(const PkDecoderPlan* p, int B, char* base, const PkAdapterStack* a
             if (need > s.ad_bytes) s.ad_bytes = need;
         }
     s.ad = c.take(s.ad_bytes);
+    s.moe_bytes = 0;
+    for (int l = 0; moe && l < p->n_layers; ++l)
+        if (moe[l].E > 0) {
+            const size_t need = pk_moerows_scratch(B, moe[l].E, p->d, moe[l].F, p->dtype);
+            if (need > s.moe_bytes) s.moe_bytes = need;
+        }
+    s.moe = c.take(s.moe_bytes);
     s.total = c.total;
     return s;
 }
 
 }  // namespace
 
+extern "C" size_t pk_decoder_step_scratch_moe(const PkDecoderPlan* plan, int B, const PkAdapterStack* adapters,
+                                              const PkMoeLayer* moe) {
+    return carve(plan, B > 0 ? B : 1, nullptr, adapters, moe).total;
+}
 extern "C" size_t pk_decoder_step_scratch_ex(const PkDecoderPlan* plan, int B, const PkAdapterStack* adapters) {
-    return carve(plan, B > 0 ? B : 1, nullptr, adapters).total;
+    return pk_decoder_step_scratch_moe(plan, B, adapters, nullptr);
 }
 extern "C" size_t pk_decoder_step_scratch(const PkDecoderPlan* plan, int B) {
     return pk_decoder_step_scratch_ex(plan, B, nullptr);
@@ -162,10 +187,10 @@ extern "C" size_t pk_decoder_step_scratch(const PkDecoderPlan* plan, int B) {
         if (rc_ != 0) return rc_; \
     } while (0)
 
-extern "C" int pk_decoder_step_ex(const PkDecoderPlan* plan, const long long* ids, int B, int t, int pos_start,
-                                  void* const* self_k, void* const* self_v, long long cap, const void* const* cross_kv,
-                                  const unsigned char* enc_mask, int S, void* scratch, size_t scratch_bytes, void* logits,
-                                  long long ld_logits, const PkAdapterStack* adapters, void* stream) {
+extern "C" int pk_decoder_step_moe(const PkDecoderPlan* plan, const long long* ids, int B, int t, int pos_start,
+                                   void* const* self_k, void* const* self_v, long long cap, const void* const* cross_kv,
+                                   const unsigned char* enc_mask, int S, void* scratch, size_t scratch_bytes, void* logits,
+                                   long long ld_logits, const PkAdapterStack* adapters, const PkMoeLayer* moe, void* stream) {
     PK_CHECK_ARG(plan && ids && self_k && self_v && cross_kv && scratch && logits, "pk_decoder_step: null argument");
     PK_CHECK_ARG(B > 0 && t >= 0 && t < cap && S > 0, "pk_decoder_step: bad sizes (B=%d t=%d cap=%lld S=%d)", B, t, cap, S);
     PK_CHECK_ARG(plan->d % 64 == 0 && plan->heads * 64 == plan->d, "pk_decoder_step: head_dim must be 64");
@@ -177,7 +202,13 @@ extern "C" int pk_decoder_step_ex(const PkDecoderPlan* plan, const long long* id
             PK_CHECK_ARG(adapters[l].a[i].down_w && adapters[l].a[i].up_w && adapters[l].a[i].p > 0,
                          "pk_decoder_step: adapter %d of layer %d is incomplete", i, l);
     }
-    Scratch s = carve(plan, B, (char*)scratch, adapters);
+    for (int l = 0; moe && l < plan->n_layers; ++l) {
+        if (moe[l].E == 0) continue;
+        PK_CHECK_ARG(moe[l].gate_w && moe[l].w1 && moe[l].w2, "pk_decoder_step: mixture of layer %d is incomplete", l);
+        PK_CHECK_ARG(pk_moerows_scratch(B, moe[l].E, plan->d, moe[l].F, plan->dtype) > 0,
+                     "pk_decoder_step: mixture of layer %d: E = %d, F = %d are not sizes pk_moerows takes", l, moe[l].E, moe[l].F);
+    }
+    Scratch s = carve(plan, B, (char*)scratch, adapters, moe);
     PK_CHECK_ARG(scratch_bytes >= s.total, "pk_decoder_step: scratch too small (%zu < %zu)", scratch_bytes, s.total);
     const int D = plan->d, H = plan->heads, F = plan->ffn, dt = plan->dtype;
     const float scale = plan->scaled_attn ? 0.125f : 1.f;
@@ -239,8 +270,13 @@ extern "C" int pk_decoder_step_ex(const PkDecoderPlan* plan, const long long* id
         RC(block_end(s.q, w.ln2_g, w.ln2_b));
         // ---- feed-forward ----
         RC(block_in(w.ln3_g, w.ln3_b, &in));
-        RC(linear(in, w.fc1_w, w.fc1_b, s.ff, F, D, plan->act));
-        RC(linear(s.ff, w.fc2_w, w.fc2_b, s.q, D, F, PK_ACT_NONE));
+        if (moe && moe[l].E > 0) {  // (fc1_* / fc2_* of such a layer are NULL)
+            RC(pk_moerows(in, s.q, moe[l].gate_w, moe[l].w1, moe[l].b1, moe[l].w2, moe[l].b2, B, moe[l].E, D, moe[l].F, plan->act, dt,
+                           s.moe, s.moe_bytes, stream));
+        } else {
+            RC(linear(in, w.fc1_w, w.fc1_b, s.ff, F, D, plan->act));
+            RC(linear(s.ff, w.fc2_w, w.fc2_b, s.q, D, F, PK_ACT_NONE));
+        }
         RC(block_end(s.q, w.ln3_g, w.ln3_b));
         // ---- the layer's adapters (AdapterTransformerDecoderLayer.forward): x <- adapter(x), into the other buffer ----
         for (int i = 0; adapters && i < adapters[l].n; ++i) {
@@ -259,6 +295,14 @@ extern "C" int pk_decoder_step_ex(const PkDecoderPlan* plan, const long long* id
     RC(pk_gemm(x, plan->out_w, logits, nullptr, nullptr, nullptr, B, plan->vocab, D, D, D, ld_logits, 0, 0, 0, 0, PK_ACT_NONE,
                0, 1.f, dt, 1, nullptr, 0, nullptr, stream));
     return 0;
+}
+
+extern "C" int pk_decoder_step_ex(const PkDecoderPlan* plan, const long long* ids, int B, int t, int pos_start,
+                                  void* const* self_k, void* const* self_v, long long cap, const void* const* cross_kv,
+                                  const unsigned char* enc_mask, int S, void* scratch, size_t scratch_bytes, void* logits,
+                                  long long ld_logits, const PkAdapterStack* adapters, void* stream) {
+    return pk_decoder_step_moe(plan, ids, B, t, pos_start, self_k, self_v, cap, cross_kv, enc_mask, S, scratch, scratch_bytes,
+                               logits, ld_logits, adapters, nullptr, stream);
 }
 
 extern "C" int pk_decoder_step(const PkDecoderPlan* plan, const long long* ids, int B, int t, int pos_start,

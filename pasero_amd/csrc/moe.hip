@@ -24,17 +24,12 @@
 // offsets[E] are neither read nor written.
 #include <cstdlib>
 #include "common.h"
+#include "moe_gate.h"
 
 namespace {
 
 constexpr int GATE_CHUNK = 256;  // tokens per counting-sort chunk
-constexpr int MOE_E_MAX = 256;
-
-__device__ __forceinline__ bool ranks_before(float va, int ia, float vb, int ib) {
-    return va > vb || (va == vb && ia < ib);
-}
-
-// one wave per token
+// one wave per token (the softmax and the top-2 choice: moe_gate.h, shared with the few-rows route kernel of moe_rows.hip)
 __global__ __launch_bounds__(256) void gate_rows_kernel(const float* __restrict__ logits, const unsigned char* __restrict__ pad,
                                                         long long S, int E, float* __restrict__ gv, int* __restrict__ top_idx,
                                                         float* __restrict__ top_w) {
@@ -51,66 +46,15 @@ __global__ __launch_bounds__(256) void gate_rows_kernel(const float* __restrict_
         }
         return;
     }
-    float v[4];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int e = lane + 64 * j;
-        v[j] = e < E ? logits[s * E + e] : -INFINITY;
-        mx = fmaxf(mx, v[j]);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    float sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        v[j] = (lane + 64 * j) < E ? expf(v[j] - mx) : 0.f;
-        sum += v[j];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    float bv[2];
     int bi[2];
-    int taken = -1;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        float cv = -1.f;
-        int ci = 0x7fffffff;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int e = lane + 64 * j;
-            if (k == 0) {
-                v[j] = v[j] / sum;
-                if (e < E) g_row[e] = v[j];
-            }
-            if (e < E && e != taken && ranks_before(v[j], e, cv, ci)) {
-                cv = v[j];
-                ci = e;
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(cv, o, 64);
-            const int oi = __shfl_xor(ci, o, 64);
-            if (ranks_before(ov, oi, cv, ci)) {
-                cv = ov;
-                ci = oi;
-            }
-        }
-        if (ci >= E) {  // nothing ranked (a row of NaN logits): a valid expert all the same, the tables are indexed by it
-            ci = (k == 1 && taken == 0) ? 1 : 0;
-            cv = 0.f;
-        }
-        bv[k] = cv;
-        bi[k] = ci;
-        taken = ci;
-    }
+    float bw[2];
+    const float* row = logits + s * E;
+    moe_gate_token([row](int e) { return row[e]; }, lane, E, g_row, bi, bw);
     if (lane == 0) {
-        const float den = bv[0] + bv[1];
         top_idx[2 * s] = bi[0];
         top_idx[2 * s + 1] = bi[1];
-        top_w[2 * s] = bv[0] / den;
-        top_w[2 * s + 1] = bv[1] / den;
+        top_w[2 * s] = bw[0];
+        top_w[2 * s + 1] = bw[1];
     }
 }
 

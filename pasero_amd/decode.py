@@ -11,7 +11,10 @@ The caches ride in the `state` dict under '_pk_decode' (`DecodeCache`); `Decoder
 search.  Layers the native step does not cover (subclass hooks, gated feed-forward, rotary positions) keep using the
 per-op path: `build_plan` returns None for them.  The layers of `adapter_transformer` (`AdapterTransformerDecoderLayer`,
 the IWSLT2023 recipes) are covered: the plan carries each layer's stack of adapters in use and the step applies them
-with pk_adapter_rows after the layer's feed-forward block (`pk_decoder_step_ex`).
+with pk_adapter_rows after the layer's feed-forward block (`pk_decoder_step_ex`).  The layers of `moe_transformer`
+(`MOETransformerDecoderLayer`, the NLLB-200 MoE checkpoints) are covered when `moe_native()` is on (off by default): the
+plan carries each mixture's gate and expert pointer tables and the step runs the feed-forward block as one pk_moerows
+call (`pk_decoder_step_moe`).  A native step does not update `moe_layer.lb_loss` (only `compute_loss` reads it).
 
 Beam search (`beam_search`, `BeamSelect`): see the section below.  Sampling search (`search`, `sampling`,
 `sample_on_the_fly`, `SampleSelect`): the reference's other decoding arm (decoding.py:906-1221 — greedy, top-k, nucleus and
@@ -59,18 +62,70 @@ class PkAdapterStack(ctypes.Structure):
     _fields_ = [('n', ctypes.c_int), ('a', PkAdapter * PK_ADAPTER_STACK_MAX)]
 
 
+class PkMoeLayer(ctypes.Structure):
+    _fields_ = [('E', ctypes.c_int), ('F', ctypes.c_int)] + [(n, _P) for n in ('gate_w', 'w1', 'b1', 'w2', 'b2')]
+
+
 class Plan:
     """the PkDecoderPlan of one TransformerDecoder plus what keeps its pointers alive / detects that they went stale;
-    `c_adapters`: the PkAdapterStack of every layer when some layer has adapters in use, else None"""
+    `c_adapters`: the PkAdapterStack of every layer when some layer has adapters in use, else None; `c_moe`: the PkMoeLayer
+    of every layer when some layer is a mixture of experts, else None"""
 
-    def __init__(self, c_plan, c_layers, keep, fingerprint, cross_w, c_adapters=None):
+    def __init__(self, c_plan, c_layers, keep, fingerprint, cross_w, c_adapters=None, c_moe=None):
         self.c_plan, self.c_layers, self.keep, self.fingerprint, self.cross_w = c_plan, c_layers, keep, fingerprint, cross_w
-        self.c_adapters = c_adapters
+        self.c_adapters, self.c_moe = c_adapters, c_moe
         self.full = None
 
     @property
     def adapters_ref(self):
         return None if self.c_adapters is None else ctypes.cast(self.c_adapters, _P)
+
+    @property
+    def moe_ref(self):
+        return None if self.c_moe is None else ctypes.cast(self.c_moe, _P)
+
+
+_moe_native = os.environ.get('PASERO_MOE_NATIVE_DECODE', '') not in ('', '0')
+
+
+def moe_native(on: Optional[bool] = None) -> bool:
+    """Native decoding for decoders with mixture-of-experts layers: sets the switch (None only asks) and returns the
+    previous setting.  Initial value: the environment variable PASERO_MOE_NATIVE_DECODE at import (unset, empty or 0: off);
+    PASERO_NO_NATIVE_DECODE still sends every call to the per-op path.  The switch is part of the plan key of decoders
+    with mixture layers: toggling it rebuilds their plan."""
+    global _moe_native
+    prev = _moe_native
+    if on is not None:
+        _moe_native = bool(on)
+    return prev
+
+
+def _has_moe(decoder) -> bool:
+    return any(hasattr(layer, 'moe_layer') for layer in decoder.layers)
+
+
+def _moe_spec(layer, D: int):
+    """(gate weight, E fc1 weights, E fc2 weights, E fc1 biases | None, E fc2 biases | None, F) of a mixture layer the native
+    step can run as pk_moerows — None when it cannot (another mixture class, lora on an expert, non-contiguous tensors)"""
+    from .moe import MixtureOfExperts
+    mix = getattr(layer, 'moe_layer', None)
+    if type(mix) is not MixtureOfExperts or mix.act_name != layer.activation_fn.name or mix.embed_dim != D:
+        return None
+    E, Fd = mix.expert_count, mix.expert_dim
+    if not 2 <= E <= 256 or len(mix.experts) != E:
+        return None
+    ex = list(mix.experts)
+    if any(getattr(m, 'lora', None) is not None for e in ex for m in (e.fc1, e.fc2)):
+        return None
+    w1, w2 = tuple(e.fc1.weight for e in ex), tuple(e.fc2.weight for e in ex)
+    b1 = tuple(e.fc1.bias for e in ex) if mix.has_bias else None
+    b2 = tuple(e.fc2.bias for e in ex) if mix.has_bias else None
+    gate = mix.gate.weight
+    tensors = [gate, *w1, *w2, *(b1 or ()), *(b2 or ())]
+    if (any(t is None or not t.is_contiguous() for t in tensors) or tuple(gate.shape) != (E, D)
+            or any(tuple(w.shape) != (Fd, D) for w in w1) or any(tuple(w.shape) != (D, Fd) for w in w2)):
+        return None
+    return gate, w1, w2, b1, b2, Fd
 
 
 def _adapter_key(decoder):
@@ -116,8 +171,10 @@ def _adapter_stack(layer, D: int):
 def _fingerprint(decoder):
     w = decoder.embed_tokens.weight
     first = decoder.layers[0]
-    fc1 = getattr(first, 'fc1', None)  # (a mixture-of-experts layer has no fc1: any parameter of the layer serves as the anchor)
-    anchor = fc1.weight if fc1 is not None else next(first.parameters())
+    fc1 = getattr(first, 'fc1', None)  # (a mixture-of-experts layer has no fc1: its gate serves as the anchor — not the
+    # attention projections, which `build_plan` moves into one packed buffer)
+    mix = getattr(first, 'moe_layer', None)
+    anchor = fc1.weight if fc1 is not None else mix.gate.weight if mix is not None else next(first.parameters())
     return (w.data_ptr(), w.dtype, str(w.device), anchor.data_ptr())
 
 
@@ -132,6 +189,7 @@ def build_plan(decoder) -> Optional[Plan]:
     """PkDecoderPlan for `decoder` (a pasero_amd TransformerDecoder), or None when a layer is not the stock one"""
     from . import modules
     from .adapters import AdapterTransformerDecoderLayer
+    from .moe import MOETransformerDecoderLayer
     from .transformer import TransformerDecoderLayer
     cfg = decoder.cfg
     if (decoder.training or not decoder.embed_tokens.weight.is_cuda
@@ -152,11 +210,19 @@ def build_plan(decoder) -> Optional[Plan]:
     def ln(m):
         return m if type(m) in (modules.LayerNorm, modules.WrappableLayerNorm, modules.LayerNormWithoutBias) else None
 
-    keep, layers, stacks = [], [], []
+    keep, layers, stacks, mixtures = [], [], [], []
     for layer in decoder.layers:
         if not isinstance(layer, TransformerDecoderLayer):
             return None
-        if type(layer) is AdapterTransformerDecoderLayer:  # exactly: a subclass may do anything around its adapters
+        spec = None
+        if _moe_native and type(layer) is MOETransformerDecoderLayer:  # exactly, and only with the switch on
+            if not layer._hooks_are_base(*[h for h in hooks if h != 'ffn']):
+                return None
+            spec = _moe_spec(layer, cfg.embed_dim)
+            if spec is None:
+                return None
+            stacks.append([])
+        elif type(layer) is AdapterTransformerDecoderLayer:  # exactly: a subclass may do anything around its adapters
             if not layer._hooks_are_base(*hooks[:-1]):
                 return None
             stack = _adapter_stack(layer, cfg.embed_dim)
@@ -167,8 +233,9 @@ def build_plan(decoder) -> Optional[Plan]:
             return None
         else:
             stacks.append([])
-        if (getattr(layer, '_no_ckpt_forward', None) is not None or layer.fc3 is not None or layer.fc1.lora is not None
-                or layer.self_attn.q_proj.lora is not None):
+        mixtures.append(spec)
+        if (getattr(layer, '_no_ckpt_forward', None) is not None or layer.fc3 is not None
+                or (spec is None and layer.fc1.lora is not None) or layer.self_attn.q_proj.lora is not None):
             return None
         norms = [ln(layer.self_attn_layer_norm), ln(layer.encoder_attn_layer_norm), ln(layer._norm_module(layer.final_layer_norm))]
         sa, ca = layer.self_attn, layer.encoder_attn
@@ -181,8 +248,8 @@ def build_plan(decoder) -> Optional[Plan]:
         keep += [w_sa, b_sa, w_ca, b_ca]
         vals = [w_sa, b_sa, sa.out_proj.weight, sa.out_proj.bias, norms[0].weight, norms[0].bias,
                 w_ca[:D], None if b_ca is None else b_ca[:D], ca.out_proj.weight, ca.out_proj.bias, norms[1].weight,
-                norms[1].bias, layer.fc1.weight, layer.fc1.bias, layer.fc2.weight, layer.fc2.bias, norms[2].weight,
-                norms[2].bias]
+                norms[1].bias, *((None,) * 4 if spec is not None else (layer.fc1.weight, layer.fc1.bias, layer.fc2.weight,
+                                                                      layer.fc2.bias)), norms[2].weight, norms[2].bias]
         layers.append((vals, (w_ca[D:], None if b_ca is None else b_ca[D:])))
     embed_ln = decoder.layernorm_embedding
     final_ln = decoder.layer_norm
@@ -221,10 +288,21 @@ def build_plan(decoder) -> Optional[Plan]:
                     setattr(ca, name, ptr(v))
                 ca.p, ca.act, ca.scaling, ca.eps = rank, act, scaling, eps
                 keep += [t for t in tensors if t is not None]  # (and under the mixed-dtype rule below)
+    c_moe = None
+    if any(m is not None for m in mixtures):
+        c_moe = (PkMoeLayer * len(mixtures))()
+        for cm, layer, spec in zip(c_moe, decoder.layers, mixtures):
+            if spec is None:
+                continue  # (E == 0: a dense layer)
+            gate, w1, w2, b1, b2, Fd = spec
+            tables = layer.moe_layer._tables.get((w1, w2, b1, b2))  # the module's own device arrays of expert addresses
+            cm.E, cm.F, cm.gate_w = len(w1), Fd, ptr(gate)
+            cm.w1, cm.w2, cm.b1, cm.b2 = (ptr(t) for t in tables)
+            keep += [gate, *w1, *w2, *(b1 or ()), *(b2 or ())] + [t for t in tables if t is not None]
     dtypes = {t.dtype for t in keep if t is not None and t.is_floating_point()}
     if len(dtypes) != 1:
         return None  # mixed parameter dtypes (e.g. fp32 LayerNorm weights in a bf16 model): per-op path, which refuses loudly
-    plan = Plan(p, c_layers, keep, _fingerprint(decoder), [cw for _, cw in layers], c_adapters)
+    plan = Plan(p, c_layers, keep, _fingerprint(decoder), [cw for _, cw in layers], c_adapters, c_moe)
     plan.full = _full_fingerprint(decoder)
     return plan
 
@@ -238,6 +316,8 @@ def get_plan(decoder) -> Optional[Plan]:
     ad_key = _adapter_key(decoder)
     if ad_key is not None:  # (decoders without adapter layers keep the two-element key)
         key += (ad_key,)
+    if _has_moe(decoder):  # (and decoders without mixture layers theirs)
+        key += (('moe_native', _moe_native),)
     cached = _plans.get(decoder)
     if cached is None or cached[0] != key:
         cached = (key, build_plan(decoder))
@@ -277,6 +357,8 @@ class DecodeCache:
 
     def _scratch_bytes(self, B: int) -> int:
         L, plan = lib.load(), self.plan
+        if plan.c_moe is not None:
+            return L.pk_decoder_step_scratch_moe(ctypes.byref(plan.c_plan), B, plan.adapters_ref, plan.moe_ref)
         if plan.c_adapters is None:
             return L.pk_decoder_step_scratch(ctypes.byref(plan.c_plan), B)
         return L.pk_decoder_step_scratch_ex(ctypes.byref(plan.c_plan), B, plan.adapters_ref)
@@ -318,7 +400,9 @@ class DecodeCache:
         L = lib.load()
         args = (ctypes.byref(self.plan.c_plan), ptr(ids), self.B, self.t, int(pos_start), self.k_tab, self.v_tab, self.cap,
                 self.c_tab, ptr(self.mask), self.S, ptr(self.scratch), self.scratch.numel(), ptr(logits), self.ldl)
-        if self.plan.c_adapters is None:
+        if self.plan.c_moe is not None:
+            check(L.pk_decoder_step_moe(*args, self.plan.adapters_ref, self.plan.moe_ref, stream_ptr()), 'pk_decoder_step_moe')
+        elif self.plan.c_adapters is None:
             check(L.pk_decoder_step(*args, stream_ptr()), 'pk_decoder_step')
         else:
             check(L.pk_decoder_step_ex(*args, self.plan.adapters_ref, stream_ptr()), 'pk_decoder_step_ex')

@@ -807,3 +807,31 @@ def moe_gemm_wgrad(dy: Tensor, x: Optional[Tensor], offsets: Tensor, dw_ptrs: Op
 def moe_use_grouped(on: int = -1) -> bool:
     """the route of the model layer's expert GEMMs (include/pasero_hip.h:pk_moe_use_grouped); returns the previous setting"""
     return bool(lib.load().pk_moe_use_grouped(int(on)))
+
+
+def moe_rows_few_max(rows: int = -1) -> int:
+    """the row threshold of pk_moerows' few-rows route (include/pasero_hip.h:pk_moerows_few_max); returns the previous one"""
+    return int(lib.load().pk_moerows_few_max(int(rows)))
+
+
+def moe_rows(x: Tensor, gate_w: Tensor, w1_ptrs: Tensor, w2_ptrs: Tensor, b1_ptrs: Optional[Tensor], b2_ptrs: Optional[Tensor],
+             expert_dim: int, act: str = 'relu', out: Optional[Tensor] = None) -> Tensor:
+    """the inference form of the mixture-of-experts layer over x (rows, D) in one native call (include/pasero_hip.h:
+    pk_moerows): gate_w (E, D); w1_ptrs / w2_ptrs / b1_ptrs / b2_ptrs: int64 device tensors of E data pointers to the experts'
+    (expert_dim, D) / (D, expert_dim) weights and their biases (or None), as `moe._PointerTables.get` builds them"""
+    require_gpu(x, gate_w, w1_ptrs, w2_ptrs, b1_ptrs, b2_ptrs, out)
+    _same(x, gate_w, what='moe_rows')
+    assert x.dim() == 2 and x.is_contiguous() and gate_w.is_contiguous() and gate_w.size(1) == x.size(1)
+    rows, D = x.shape
+    E = gate_w.size(0)
+    for t in (w1_ptrs, w2_ptrs, b1_ptrs, b2_ptrs):
+        assert t is None or (t.dtype == torch.int64 and t.numel() == E)
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == x.dtype and out.is_contiguous()
+    L = lib.load()
+    nbytes = L.pk_moerows_scratch(rows, E, D, int(expert_dim), dtype_code(x))
+    scratch = lib.workspace(nbytes, x.device, 'moe_rows')
+    check(L.pk_moerows(ptr(x), ptr(out), ptr(gate_w), ptr(w1_ptrs), ptr(b1_ptrs), ptr(w2_ptrs), ptr(b2_ptrs), rows, E, D,
+                       int(expert_dim), ACT[act], dtype_code(x), ptr(scratch), nbytes, stream_ptr()), 'pk_moerows')
+    return out

@@ -108,6 +108,13 @@ SIGNATURES = {
     'pk_moe_gemm': (I, [P, P, P, P, P, P, P, LL, I, LL, LL, I, I, I, I, P]),
     'pk_moe_gemm_wgrad': (I, [P, P, P, P, P, LL, I, LL, LL, I, P]),
     'pk_moe_use_grouped': (I, [I]),
+    'pk_moerows_route': (I, [P, LL, I, I, P, P, P, P, P, P]),
+    'pk_moerows_few': (I, [LL, I, I, I, I]),
+    'pk_moerows_few_max': (I, [I]),
+    'pk_moerows_scratch': (SZ, [LL, I, I, I, I]),
+    'pk_moerows': (I, [P, P, P, P, P, P, P, LL, I, I, I, I, I, P, SZ, P]),
+    'pk_decoder_step_scratch_moe': (SZ, [P, I, P, P]),
+    'pk_decoder_step_moe': (I, [P, P, I, I, I, P, P, LL, P, P, I, P, SZ, P, LL, P, P, P]),
 }
 
 PK_WGRAD_MAX = 8

@@ -14,8 +14,10 @@ leaves its `.grad` at None (knowing it was unused would need a host read).
 
 Not implemented, refused at construction: `moe_impl='tutel'` (third-party package, expert parallelism), `moe_impl='fused'`
 (the reference's own constructor fails; its checkpoint layout still loads), gated (swiglu / geglu) experts, tensor
-parallelism.  `capacity_factor` is Tutel's and has no effect in `basic`.  MoE layers take the per-op layer path and MoE
-decoders the per-op decoding path (`decode.build_plan` returns None for an overridden `ffn`).
+parallelism.  `capacity_factor` is Tutel's and has no effect in `basic`.  MoE layers take the per-op layer path.  MoE
+decoders take the per-op decoding path by default (`decode.build_plan` returns None for an overridden `ffn`); with
+`decode.moe_native(True)` (or PASERO_MOE_NATIVE_DECODE=1) their incremental calls run as one native step whose mixture blocks
+are pk_moerows calls (csrc/moe_rows.hip: one-launch routing and few-rows expert GEMMs) — that step does not update `lb_loss`.
 """
 import logging
 from typing import Optional
@@ -305,7 +307,8 @@ def _refuse(cfg, dist_cfg):
 
 class _MOELayerMixin:
     """a Transformer layer whose feed-forward block is a mixture of experts (mixture_of_experts.py:405-478): no fc1 / fc2 /
-    fc3, `ffn` overridden (so the fused block tails, the one-call layer and the native decoding step all step aside)"""
+    fc3, `ffn` overridden (so the fused block tails and the one-call layer step aside, and the native decoding step too unless
+    `decode.moe_native` is on)"""
 
     def _build_moe(self, cfg, dist_cfg, side: str, ffn_dim: int):
         _refuse(cfg, dist_cfg)
