@@ -713,6 +713,43 @@ int pk_decoder_step_moe(const PkDecoderPlan* plan, const long long* ids, int B, 
                         int S, void* scratch, size_t scratch_bytes, void* logits, long long ld_logits,
                         const PkAdapterStack* adapters, const PkMoeLayer* moe, void* stream);
 
+/* ---- `hybrid_transformer`'s LSTM decoder (csrc/lstm.hip, csrc/addattn.hip; pasero/models/hybrid.py) ----
+ * Every argument is checked before any launch; no allocation, no synchronisation.  Tensors are contiguous in the layouts
+ * given unless a stride is named; strides are in elements.
+ *
+ * pk_lstm_fwd: the recurrence of one LSTM layer, gate order i, f, g, o, ONE launch per time step:
+ *     pre_t = gx[b, t] + b_hh + h_{t-1} w_hh^T     c_t = f c_{t-1} + i g     h_t = o tanh(c_t)
+ *   gx [B][T][4H] with batch stride gx_ldb and time stride gx_ldt (multiples of 8, >= 4H): the input-side product with its
+ *   bias, computed by the caller.  w_hh [4H][H], b_hh [4H].  h0 / c0 [B][H] or both NULL (zero state).
+ *   Outputs: y [B][T][H] (h_t), c [B][T][H], gates [B][T][4H] (the ACTIVATED gates, what backward reads), hT / cT [B][H] or NULL.
+ *   h_t, c_t and the gates are rounded to the storage type at every step (c_t before tanh(c_t)): a T-step call equals T
+ *   one-step calls bit for bit, and a row's result does not depend on the other rows of the call.  H % 16 == 0.
+ * pk_lstm_bwd: dgates [B][T][4H] (= d gx) from dy [B][T][H], one launch per step from t = T-1 down; c0 [B][H] or NULL is the
+ *   forward's; no gradient towards h0 / c0.  dW_hh, db_hh and the input-side gradients are (B T)-row products of dgates, left to
+ *   the caller.  scratch: pk_lstm_bwd_scratch bytes (the fp32 carry of dc and w_hh transposed).  `y` is not read (NULL allowed).
+ *
+ * pk_addattn_fwd: additive single-head attention without the (B, T, S, H) intermediate:
+ *     score[b,t,s] = sum_h w[h] tanh(k[b,s,h] + q[b,t,h]);  probs = softmax over s, keys with key_pad[b,s] != 0 excluded;
+ *     ctx[b,t,:] = sum_s probs[b,t,s] value[b,s,:]
+ *   q [B][T][H], k [B][S][H] (projection outputs, biases included), w [H], key_pad [B][S] bytes or NULL, value [B][S][D];
+ *   probs [B][T][S] in the storage type (exactly 0 at excluded keys), ctx [B][T][D].  A sentence without any real key is
+ *   undefined.  H % 16 == 0, D % 8 == 0; the scores of 8 queries live in LDS: (9 H + 8 S) * 4 bytes <= 160 KiB.
+ * pk_addattn_bwd: dq, dk, dw [H], dvalue from dctx and the forward's probs; deterministic (no atomics: a pass tiled over
+ *   queries, a pass tiled over keys, dw from per-workgroup partial rows added in a fixed tree).  scratch:
+ *   pk_addattn_bwd_scratch bytes; LDS (13 H + 8 D + 8 S) * 4 bytes <= 160 KiB (H = D = 1024: S <= 2432). */
+size_t pk_lstm_bwd_scratch(long long B, int H, int dtype);
+int pk_lstm_fwd(const void* gx, long long gx_ldb, long long gx_ldt, const void* w_hh, const void* b_hh, const void* h0,
+                const void* c0, void* y, void* c, void* gates, void* hT, void* cT, long long B, long long T, int H, int dtype,
+                void* stream);
+int pk_lstm_bwd(const void* dy, const void* w_hh, const void* y, const void* c, const void* gates, const void* c0,
+                void* dgates, long long B, long long T, int H, int dtype, void* scratch, size_t scratch_bytes, void* stream);
+size_t pk_addattn_bwd_scratch(int B, int T, int S, int H);
+int pk_addattn_fwd(const void* q, const void* k, const void* w, const unsigned char* key_pad, const void* value, void* probs,
+                   void* ctx, int B, int T, int S, int H, int D, int dtype, void* stream);
+int pk_addattn_bwd(const void* dctx, const void* q, const void* k, const void* w, const void* value, const void* probs,
+                   void* dq, void* dk, void* dw, void* dvalue, int B, int T, int S, int H, int D, int dtype, void* scratch,
+                   size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

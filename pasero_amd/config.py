@@ -341,3 +341,67 @@ class MOETransformerBigConfig(_MOEOptions, TransformerBigConfig):
 @dataclass
 class MOETransformerWideConfig(_MOEOptions, TransformerWideConfig):
     pass
+
+
+@dataclass
+class _HybridOptions:   # config.py:1391-1416 (what `hybrid_transformer` changes in and adds to a backbone configuration)
+    decoder_layers: int = 2            # LSTM layers
+    decoder_hidden_size: int = 512     # hidden size of the LSTMs
+    decoder_embed_proj: bool = False   # a linear projection of the decoder's input embeddings before the first LSTM
+    _arch = 'hybrid_transformer'
+
+
+@register_model_config('hybrid_transformer')
+@dataclass
+class HybridTransformerConfig(_HybridOptions, TransformerConfig):
+    pass
+
+
+@register_model_config('adapter_hybrid_transformer')
+@dataclass
+class AdapterHybridTransformerConfig(_HybridOptions, AdapterTransformerConfig):
+    _arch = 'adapter_hybrid_transformer'
+
+
+# hybrid_* presets (config.py:2203-2213, 2474-2493): only the encoder's sizes and the LSTM width change
+@register_model_config('hybrid_transformer_big', 'rnmt_big')
+@dataclass
+class HybridTransformerBigConfig(HybridTransformerConfig):
+    embed_dim: int = 1024
+    encoder_ffn_dim: int = 4096
+    encoder_attention_heads: int = 16
+    decoder_hidden_size: int = 1024
+
+
+@register_model_config('hybrid_transformer_wide')
+@dataclass
+class HybridTransformerWideConfig(HybridTransformerBigConfig):
+    encoder_ffn_dim: int = 8192
+    decoder_hidden_size: int = 2048
+
+
+@register_model_config('hybrid_transformer_small')
+@dataclass
+class HybridTransformerSmallConfig(HybridTransformerConfig):
+    embed_dim: int = 512
+    encoder_ffn_dim: int = 1024
+    decoder_ffn_dim: int = 1024
+    encoder_attention_heads: int = 4
+    decoder_attention_heads: int = 4
+    decoder_hidden_size: int = 512
+
+
+@register_model_config('adapter_hybrid_transformer_big')
+@dataclass
+class AdapterHybridTransformerBigConfig(AdapterHybridTransformerConfig):
+    embed_dim: int = 1024
+    encoder_ffn_dim: int = 4096
+    encoder_attention_heads: int = 16
+    decoder_hidden_size: int = 1024
+
+
+@register_model_config('adapter_hybrid_transformer_wide')
+@dataclass
+class AdapterHybridTransformerWideConfig(AdapterHybridTransformerBigConfig):
+    encoder_ffn_dim: int = 8192
+    decoder_hidden_size: int = 2048

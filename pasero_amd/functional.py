@@ -835,3 +835,91 @@ def moe_rows(x: Tensor, gate_w: Tensor, w1_ptrs: Tensor, w2_ptrs: Tensor, b1_ptr
     check(L.pk_moerows(ptr(x), ptr(out), ptr(gate_w), ptr(w1_ptrs), ptr(b1_ptrs), ptr(w2_ptrs), ptr(b2_ptrs), rows, E, D,
                        int(expert_dim), ACT[act], dtype_code(x), ptr(scratch), nbytes, stream_ptr()), 'pk_moerows')
     return out
+
+
+# ---- the LSTM decoder of `hybrid_transformer` (csrc/lstm.hip, csrc/addattn.hip) ----
+def _outputs(out, shapes, like: Tensor):
+    """the output tensors of a call: new ones, or the caller's `out` (checked: shapes, dtype, contiguous)"""
+    if out is None:
+        return tuple(torch.empty(*s, dtype=like.dtype, device=like.device) for s in shapes)
+    assert len(out) == len(shapes)
+    for t, s in zip(out, shapes):
+        assert tuple(t.shape) == tuple(s) and t.dtype == like.dtype and t.is_contiguous() and t.device == like.device
+    return tuple(out)
+
+
+def lstm_fwd(gx: Tensor, w_hh: Tensor, b_hh: Tensor, h0: Optional[Tensor] = None, c0: Optional[Tensor] = None, out=None):
+    """the recurrence of one LSTM layer (include/pasero_hip.h:pk_lstm_fwd): gx (B, T, 4H) with unit inner stride — the
+    input-side product, its bias included — w_hh (4H, H), b_hh (4H,), h0 / c0 (B, H) or None.
+    -> y (B, T, H), c (B, T, H), the activated gates (B, T, 4H), hT, cT (B, H); `out`: these five, allocated by the caller"""
+    require_gpu(gx, w_hh, b_hh, h0, c0)
+    _same(gx, w_hh, b_hh, h0, c0, what='lstm_fwd')
+    B, T, G = gx.shape
+    H = G // 4
+    assert gx.stride(2) == 1 and w_hh.shape == (G, H) and w_hh.is_contiguous() and b_hh.shape == (G,) and b_hh.is_contiguous()
+    for s in (h0, c0):
+        assert s is None or (s.shape == (B, H) and s.is_contiguous())
+    y, c, gates, hT, cT = _outputs(out, [(B, T, H), (B, T, H), (B, T, G), (B, H), (B, H)], gx)
+    ldb = gx.stride(0) if B > 1 else max(gx.stride(0), T * gx.stride(1))
+    check(lib.load().pk_lstm_fwd(ptr(gx), ldb, gx.stride(1) if T > 1 else max(gx.stride(1), G), ptr(w_hh), ptr(b_hh), ptr(h0),
+                                 ptr(c0), ptr(y), ptr(c), ptr(gates), ptr(hT), ptr(cT), B, T, H, dtype_code(gx), stream_ptr()),
+          'pk_lstm_fwd')
+    return y, c, gates, hT, cT
+
+
+def lstm_bwd(dy: Tensor, w_hh: Tensor, c: Tensor, gates: Tensor, c0: Optional[Tensor] = None, out=None) -> Tensor:
+    """d gx (B, T, 4H) of `lstm_fwd` from dy (B, T, H) and what the forward saved (include/pasero_hip.h:pk_lstm_bwd)"""
+    require_gpu(dy, w_hh, c, gates, c0)
+    _same(dy, w_hh, c, gates, c0, what='lstm_bwd')
+    B, T, H = dy.shape
+    assert dy.is_contiguous() and c.is_contiguous() and gates.is_contiguous() and w_hh.is_contiguous()
+    assert c.shape == (B, T, H) and gates.shape == (B, T, 4 * H) and w_hh.shape == (4 * H, H)
+    assert c0 is None or (c0.shape == (B, H) and c0.is_contiguous())
+    dg, = _outputs(None if out is None else (out,), [gates.shape], gates)
+    L = lib.load()
+    nbytes = L.pk_lstm_bwd_scratch(B, H, dtype_code(dy))
+    scratch = lib.workspace(nbytes, dy.device, 'lstm')
+    check(L.pk_lstm_bwd(ptr(dy), ptr(w_hh), None, ptr(c), ptr(gates), ptr(c0), ptr(dg), B, T, H, dtype_code(dy), ptr(scratch),
+                        nbytes, stream_ptr()), 'pk_lstm_bwd')
+    return dg
+
+
+def _pad_bytes(key_pad: Optional[Tensor], B: int, S: int) -> Optional[Tensor]:
+    if key_pad is None:
+        return None
+    assert key_pad.shape == (B, S) and key_pad.dtype in (torch.bool, torch.uint8) and key_pad.is_contiguous()
+    return key_pad.view(torch.uint8) if key_pad.dtype == torch.bool else key_pad
+
+
+def addattn_fwd(q: Tensor, k: Tensor, w: Tensor, key_pad: Optional[Tensor], value: Tensor, out=None):
+    """additive attention (include/pasero_hip.h:pk_addattn_fwd): q (B, T, H), k (B, S, H), w (H,), key_pad (B, S) bool / uint8
+    or None, value (B, S, D) -> probs (B, T, S), ctx (B, T, D)"""
+    require_gpu(q, k, w, key_pad, value)
+    _same(q, k, w, value, what='addattn_fwd')
+    B, T, H = q.shape
+    S, D = k.size(1), value.size(2)
+    assert k.shape == (B, S, H) and value.shape == (B, S, D) and w.numel() == H
+    assert q.is_contiguous() and k.is_contiguous() and value.is_contiguous() and w.is_contiguous()
+    pad = _pad_bytes(key_pad, B, S)
+    probs, ctx = _outputs(out, [(B, T, S), (B, T, D)], q)
+    check(lib.load().pk_addattn_fwd(ptr(q), ptr(k), ptr(w), ptr(pad), ptr(value), ptr(probs), ptr(ctx), B, T, S, H, D,
+                                    dtype_code(q), stream_ptr()), 'pk_addattn_fwd')
+    return probs, ctx
+
+
+def addattn_bwd(dctx: Tensor, q: Tensor, k: Tensor, w: Tensor, value: Tensor, probs: Tensor, out=None):
+    """-> dq, dk, dw, dvalue of `addattn_fwd` (include/pasero_hip.h:pk_addattn_bwd); deterministic"""
+    require_gpu(dctx, q, k, w, value, probs)
+    _same(q, dctx, k, w, value, probs, what='addattn_bwd')
+    B, T, H = q.shape
+    S, D = k.size(1), value.size(2)
+    assert dctx.shape == (B, T, D) and probs.shape == (B, T, S) and k.shape == (B, S, H) and value.shape == (B, S, D)
+    for t in (dctx, q, k, w, value, probs):
+        assert t.is_contiguous()
+    dq, dk, dw, dvalue = _outputs(out, [q.shape, k.shape, w.shape, value.shape], q)
+    L = lib.load()
+    nbytes = L.pk_addattn_bwd_scratch(B, T, S, H)
+    scratch = lib.workspace(nbytes, q.device, 'addattn')
+    check(L.pk_addattn_bwd(ptr(dctx), ptr(q), ptr(k), ptr(w), ptr(value), ptr(probs), ptr(dq), ptr(dk), ptr(dw), ptr(dvalue),
+                           B, T, S, H, D, dtype_code(q), ptr(scratch), nbytes, stream_ptr()), 'pk_addattn_bwd')
+    return dq, dk, dw, dvalue

@@ -115,6 +115,12 @@ SIGNATURES = {
     'pk_moerows': (I, [P, P, P, P, P, P, P, LL, I, I, I, I, I, P, SZ, P]),
     'pk_decoder_step_scratch_moe': (SZ, [P, I, P, P]),
     'pk_decoder_step_moe': (I, [P, P, I, I, I, P, P, LL, P, P, I, P, SZ, P, LL, P, P, P]),
+    'pk_lstm_bwd_scratch': (SZ, [LL, I, I]),
+    'pk_lstm_fwd': (I, [P, LL, LL, P, P, P, P, P, P, P, P, P, LL, LL, I, I, P]),
+    'pk_lstm_bwd': (I, [P, P, P, P, P, P, P, LL, LL, I, I, P, SZ, P]),
+    'pk_addattn_bwd_scratch': (SZ, [I, I, I, I]),
+    'pk_addattn_fwd': (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+    'pk_addattn_bwd': (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, SZ, P]),
 }
 
 PK_WGRAD_MAX = 8
