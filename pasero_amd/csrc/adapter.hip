@@ -32,17 +32,6 @@
 #include <cstdlib>
 #include "common.h"
 
-extern "C" {
-int pk_gemm(const void* A, const void* B, void* C, const void* bias, const void* aux, void* preact, long long M,
-            long long N, long long K, long long lda, long long ldb, long long ldc, long long ldaux, long long ldpre,
-            int a_col, int b_col, int act, int mode, float alpha, int dtype, int splitk, void* workspace,
-            size_t ws_bytes, void* asum_out, void* stream);
-int pk_residual_ln_fwd(const void* x, const void* residual, const void* gamma, const void* beta, void* z_out,
-                       void* y_out, float* mean, float* rstd, long long rows, int d, float eps, float drop_p,
-                       unsigned long long seed, unsigned long long offset, int dtype, void* stream);
-int pk_scale(const void* x, void* out, long long n, const float* dev_scalar, float host_scalar, int dtype, void* stream);
-}
-
 namespace {
 
 constexpr int AD_BM = 32, AD_WAVES = 4, AD_PAD = 8, AD_LDS_MAX = 160 * 1024;

@@ -2,6 +2,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
+#include "internal.h"
 
 static thread_local char g_err[512] = "";
 

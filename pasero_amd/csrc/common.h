@@ -4,25 +4,7 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 
-#define PK_F32 0
-#define PK_BF16 1
-#define PK_F16 2
-
-// activation ids (pasero/models/modules.py:220-228)
-// (include/pasero_hip.h: deferred LayerNorm parameter gradients)
-#define PK_LN_GROUP_MAX 4
-struct PkLnParamGrad {
-    const void* workspace;
-    void* dgamma;
-    void* dbeta;
-};
-#define PK_GEMM_PAD_N 1 /* pk_gemm_ex promises (include/pasero_hip.h) */
-#define PK_GEMM_PAD_K 2
-#define PK_ACT_NONE 0
-#define PK_ACT_RELU 1
-#define PK_ACT_GELU 2       // erf
-#define PK_ACT_GELU_TANH 3
-#define PK_ACT_SILU 4
+#include "internal.h"  // the C ABI (include/pasero_hip.h: dtype / activation ids, structs) + cross-file launchers
 
 typedef __hip_bfloat16 bf16;
 typedef _Float16 f16;  // IEEE half: the reference's default training dtype (config.py:518-523)
@@ -30,8 +12,6 @@ typedef __attribute__((ext_vector_type(8))) short bf16x8;   // MFMA bf16 A/B fra
 typedef __attribute__((ext_vector_type(4))) short bf16x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;  // 32x32 MFMA accumulator
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-extern "C" void pk_set_error(const char* fmt, ...);
 
 #define PK_CHECK_ARG(cond, ...)                 \
     do {                                        \

@@ -13,77 +13,6 @@
 #include <utility>
 #include "common.h"
 
-extern "C" {
-int pk_gemm(const void* A, const void* B, void* C, const void* bias, const void* aux, void* preact, long long M,
-            long long N, long long K, long long lda, long long ldb, long long ldc, long long ldaux, long long ldpre,
-            int a_col, int b_col, int act, int mode, float alpha, int dtype, int splitk, void* workspace,
-            size_t ws_bytes, void* asum_out, void* stream);
-int pk_residual_ln_fwd(const void* x, const void* residual, const void* gamma, const void* beta, void* z_out,
-                       void* y_out, float* mean, float* rstd, long long rows, int d, float eps, float drop_p,
-                       unsigned long long seed, unsigned long long offset, int dtype, void* stream);
-int pk_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const unsigned char* key_pad,
-                int B, int H, int T, int S, int hd, long long q_bs, long long q_rs, long long k_bs, long long k_rs,
-                long long v_bs, long long v_rs, long long o_bs, long long o_rs, int causal, float scale, float drop_p,
-                unsigned long long seed, unsigned long long offset, unsigned char* drop_mask, int dtype, void* stream);
-int pk_embed_fwd(const long long* ids, const void* E, const void* pos, void* out, long long ntok, int Tlen, int d,
-                 long long V, float scale, int pos_start, float drop_p, unsigned long long seed,
-                 unsigned long long offset, int dtype, void* stream);
-size_t pk_adapter_rows_step_scratch(long long rows, int d, int p, int dtype);
-int pk_adapter_rows_step(const void* x, void* y, const void* ln_g, const void* ln_b, const void* down_w, const void* down_b,
-                    const void* up_w, const void* up_b, long long rows, int d, int p, int act, float scaling, float eps,
-                    int dtype, void* scratch, size_t scratch_bytes, void* stream);
-size_t pk_moerows_scratch(long long rows, int E, int D, int F, int dtype);
-int pk_moerows(const void* x, void* y, const void* gate_w, const void* const* w1, const void* const* b1,
-                const void* const* w2, const void* const* b2, long long rows, int E, int D, int F, int act, int dtype,
-                void* scratch, size_t scratch_bytes, void* stream);
-}
-
-// ---- plan: mirrors include/pasero_hip.h (PkDecoderLayerWeights / PkDecoderPlan) ----
-struct PkDecoderLayerWeights {
-    const void *qkv_w, *qkv_b;    // self-attention packed projection [3D][D], [3D]
-    const void *out_w, *out_b;    // self-attention output projection [D][D]
-    const void *ln1_g, *ln1_b;    // self_attn_layer_norm
-    const void *cq_w, *cq_b;      // cross-attention query projection [D][D]
-    const void *cout_w, *cout_b;  // cross-attention output projection
-    const void *ln2_g, *ln2_b;    // encoder_attn_layer_norm
-    const void *fc1_w, *fc1_b;    // [F][D]
-    const void *fc2_w, *fc2_b;    // [D][F]
-    const void *ln3_g, *ln3_b;    // final_layer_norm
-};
-struct PkDecoderPlan {
-    int n_layers, d, heads, ffn, act, prenorm, dtype, scaled_attn;
-    long long vocab;
-    float eps, embed_scale;
-    const void* embed;        // [V][D] token embedding
-    const void* pos;          // positional table rows [.][D] or NULL
-    const void* embed_ln_g;   // layernorm_embedding (NULL = Identity)
-    const void* embed_ln_b;
-    const void* final_ln_g;   // decoder.layer_norm (pre-norm stacks; NULL = Identity)
-    const void* final_ln_b;
-    const void* out_w;        // output projection [V][D] (the embedding itself when tied)
-    const PkDecoderLayerWeights* layers;
-};
-// the adapters of a layer, applied in order after its feed-forward block end (adapters.py:232-301)
-#define PK_ADAPTER_STACK_MAX 4
-struct PkAdapter {
-    const void *ln_g, *ln_b, *down_w, *down_b, *up_w, *up_b;
-    int p, act;
-    float scaling, eps;
-};
-struct PkAdapterStack {
-    int n;
-    PkAdapter a[PK_ADAPTER_STACK_MAX];
-};
-// a layer whose feed-forward block is a mixture of experts (E == 0: a dense layer)
-struct PkMoeLayer {
-    int E, F;
-    const void* gate_w;
-    const void* const* w1;   /* device arrays of E device pointers, as pk_moe_gemm takes them; b1 / b2 may be NULL */
-    const void* const* b1;
-    const void* const* w2;
-    const void* const* b2;
-};
-
 namespace {
 
 // append this step's K and V rows (columns [D, 3D) of the packed projection) to the per-layer caches at position t

@@ -30,32 +30,6 @@
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
-extern "C" int pk_gemm256_launch(const void* A, const void* B, void* C, float* ws, float* asum_ws, void* asum_out,
-                                 long long M, long long N, long long K, long long lda, long long ldb, int a_col,
-                                 int b_col, int kchunk, int splitk, EpiParams ep, int dtype, void* stream);
-extern "C" int pk_gemm8p_is_pw(long long M, long long N, long long K, long long lda, long long ldb, int a_col, int b_col,
-                               int splitk, int has_ws, int has_asum, const EpiParams* ep);
-extern "C" int pk_gemm8p_is_pt(long long M, long long N, long long K, long long lda, long long ldb, int a_col, int b_col,
-                               int splitk, int has_ws, int has_asum, const EpiParams* ep);
-extern "C" int pk_gemm8p_launch(const void* A, const void* B, void* C, float* ws, float* asum_ws, void* asum_out,
-                                long long M, long long N, long long K, long long lda, long long ldb, int a_col,
-                                int b_col, int kchunk, int splitk, EpiParams ep, int dtype, void* stream);
-extern "C" int pk_gemm8p_eligible(long long M, long long N, long long K, long long lda, long long ldb, int a_col,
-                                  int b_col, int want_asum);
-extern "C" int pk_gemm8p_group_eligible(const PkWgradProblem* q);
-extern "C" int pk_gemm8p_group_plan(const PkWgradProblem* p, int n, size_t* ws_bytes, int* workgroups, int* slabs);
-extern "C" int pk_gemm8p_group_map(const PkWgradProblem* p, int n, int* out, int cap);
-extern "C" int pk_gemm8p_group_launch(const PkWgradProblem* p, int n, int dtype, float* workspace, void* stream);
-extern "C" int pk_gemm8p_group_reduce(const PkWgradProblem* p, int n, int dtype, float* workspace, void* stream);
-extern "C" int pk_gemmln_spec(int has_residual, float drop_p, long long K);
-extern "C" int pk_gemmln_launch(const void* A, const void* W, const void* bias, const void* residual, const void* gamma,
-                                const void* beta, void* z_out, void* y_out, float* mean, float* rstd, long long M,
-                                long long N, long long K, long long lda, long long ldb, long long ldr, float eps,
-                                float drop_p, unsigned long long seed, unsigned long long offset, int dtype,
-                                void* stream);
-extern "C" int pk_gemm_skinny_launch(const void* A, const void* B, void* C, long long M, long long N, long long K,
-                                     long long lda, long long ldb, EpiParams ep, int dtype, void* stream);
-
 namespace {
 
 constexpr int BM = 128, BN = 128, NTHREADS = 256;
@@ -731,14 +705,6 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ ws, T* __restrict
 }
 
 // PK_GEMM_8P=0 / pk_gemm_use_8p(0): keep the 256-tile GEMMs on gemm256.hip (A/B of the two K loops inside one process)
-// B-stationary kernel for K = 512 / 256 (gemmbs.hip)
-extern "C" int pk_gemmbs_eligible(const void* A, const void* B, const void* C, long long M, long long N, long long K,
-                                  long long lda, long long ldb, int a_col, int b_col, const EpiParams* ep);
-extern "C" int pk_gemmbs_launch(const void* A, const void* B, void* C, long long M, long long N, long long K,
-                                long long lda, long long ldb, int b_col, EpiParams ep, int dtype, void* stream,
-                                unsigned char* bits, long long ldbits);
-extern "C" int pk_gemmbs_use(int on);
-
 int g_use_8p = [] { const char* e = getenv("PK_GEMM_8P"); return (!e || atoi(e) != 0) ? 1 : 0; }();
 
 // ---- optional launch timing (bench.py's roofline leg): HIP events around exactly the main GEMM kernel, on its stream ----
@@ -974,12 +940,6 @@ int launch_gemm(const void* A, const void* B, void* C, long long M, long long N,
 }
 
 }  // namespace
-
-extern "C" int pk_gemm_ex(const void* A, const void* B, void* C, const void* bias, const void* aux, void* preact,
-                          long long M, long long N, long long K, long long lda, long long ldb, long long ldc,
-                          long long ldaux, long long ldpre, int a_col, int b_col, int act, int mode, float alpha,
-                          int dtype, int splitk, void* workspace, size_t ws_bytes, void* asum_out, int pad_flags,
-                          void* stream);
 
 extern "C" int pk_gemm(const void* A, const void* B, void* C, const void* bias, const void* aux, void* preact,
                        long long M, long long N, long long K, long long lda, long long ldb, long long ldc,

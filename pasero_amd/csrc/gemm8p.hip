@@ -1257,13 +1257,6 @@ extern "C" int pk_gemm8p_eligible(long long M, long long N, long long K, long lo
     return a_bytes <= lim && b_bytes <= lim;
 }
 
-// The persistent 128 x 256-tile kernel (gemmpw.hip, round 6): row-form A, whole K-tiles, many rounds of tiles, lean epilogue.
-extern "C" int pk_gemmpw_eligible(long long M, long long N, long long K, long long lda, long long ldb, long long ldc, int b_col,
-                                  const EpiParams* ep);
-extern "C" int pk_gemmpw_launch(const void* A, const void* B, void* C, long long M, long long N, long long K, long long lda,
-                                long long ldb, unsigned a_bytes, unsigned b_bytes, int b_col, EpiParams ep, int dtype,
-                                void* stream);
-extern "C" int pk_gemm_use_pw(int on);
 // 1 if pk_gemm8p_launch runs this call as the persistent walk of 256 x 256 tiles (gemm8p_tile's PW form, gemm8p_pt_kernel):
 // row-form A, an even number (>= 4) of whole K-tiles, no split, a lean or mask-bit epilogue, at least `PK_GEMM_PT_MIN_TILES`
 // (default 512: two rounds of the chip) tiles.  Bit 1 of pk_gemm_use_pw (default on; env PK_GEMM_PW sets the mask).

@@ -19,13 +19,3 @@ struct EpiParams {
     long long ldbits = 0;
 };
 
-// One weight-gradient problem of a grouped launch (include/pasero_hip.h: PkWgradProblem): C[M,N] = A^T B, both operands
-// in col form (A = dY [K][lda], B = X [K][ldb]), asum_out[m] = sum_k A(m,k) (optional bias gradient)
-#define PK_WGRAD_MAX 8
-struct PkWgradProblem {
-    const void* A;
-    const void* B;
-    void* C;
-    void* asum_out;
-    long long M, N, K, lda, ldb, ldc;
-};

@@ -7,9 +7,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <algorithm>
-#include "../../include/pasero_hip.h"
-
-extern "C" void pk_set_error(const char* fmt, ...);
+#include "internal.h"
 
 namespace {
 

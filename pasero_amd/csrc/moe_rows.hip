@@ -18,26 +18,6 @@
 #include "common.h"
 #include "moe_gate.h"
 
-#define PK_MOE_ROWS_MAX 1024
-
-extern "C" {
-int pk_gemm(const void* A, const void* B, void* C, const void* bias, const void* aux, void* preact, long long M,
-            long long N, long long K, long long lda, long long ldb, long long ldc, long long ldaux, long long ldpre,
-            int a_col, int b_col, int act, int mode, float alpha, int dtype, int splitk, void* workspace,
-            size_t ws_bytes, void* asum_out, void* stream);
-size_t pk_moe_gate_scratch(long long S, int E);
-int pk_moe_gate(const float* logits, const unsigned char* pad, long long S, int E, float* gate_value, int* top_idx,
-                float* top_w, int* top1_count, float* prob_sum, float* lb_coef, float* lb_loss, int* offsets, int* slot_of,
-                int* token_of, void* scratch, size_t scratch_bytes, void* stream);
-int pk_moe_gather(const void* X, void* Xg, const int* token_of, const int* offsets, const int* slot_of, const float* top_w,
-                  long long S, int E, int D, int dtype, void* stream);
-int pk_moe_combine(const void* Y, void* out, const int* slot_of, const float* top_w, long long S, int D, int dtype,
-                   void* stream);
-int pk_moe_gemm(const void* A, const void* const* W, const void* const* bias, void* C, const void* aux, void* preact,
-                const int* offsets, long long rows, int E, long long N, long long K, int b_col, int act, int mode, int dtype,
-                void* stream);
-}
-
 namespace {
 
 constexpr int ROUTE_THREADS = 1024;

@@ -17,7 +17,9 @@ ACT = {'none': 0, None: 0, 'relu': 1, 'gelu': 2, 'gelu_tanh': 3, 'geglu': 3, 'sw
 
 P, I, F, LL, SZ, ULL = c_void_p, c_int, c_float, c_longlong, c_size_t, c_ulonglong
 
-# name -> (restype, argtypes); must stay in sync with include/pasero_hip.h (tests/test_boundary_cpu.py checks the symbols)
+# name -> (restype, argtypes), typed by hand from include/pasero_hip.h.  tests/test_boundary_cpu.py holds it to the header:
+# the same set of names as the header and the library's exports, and for every function the return type and each
+# argument's type as parsed from the header's prototype (any pointer = P, `const char*` = c_char_p)
 SIGNATURES = {
     'pk_version': (I, []),
     'pk_last_error': (c_char_p, []),

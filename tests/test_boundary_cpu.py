@@ -29,6 +29,60 @@ def test_library_exports_every_header_symbol():
     assert L.pk_version() >= 100
 
 
+def _header_prototypes():
+    """{name: (return type, [parameter types])} of every function include/pasero_hip.h declares, as ctypes types.  Any pointer
+    is c_void_p, except that exactly `const char*` is c_char_p; a type that is not listed here is an error."""
+    import ctypes
+    scalars = {'unsigned long long': ctypes.c_ulonglong, 'long long': ctypes.c_longlong, 'size_t': ctypes.c_size_t,
+               'float': ctypes.c_float, 'int': ctypes.c_int}
+
+    def ctype(tokens, where):
+        if '*' in tokens:
+            return ctypes.c_char_p if tokens == ['const', 'char', '*'] else ctypes.c_void_p
+        assert ' '.join(tokens) in scalars, f'{where}: no ctypes counterpart known for `{" ".join(tokens)}`'
+        return scalars[' '.join(tokens)]
+
+    text = open(os.path.join(ROOT, 'include', 'pasero_hip.h')).read()
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)              # comments (the header has no // ones, C89 style; strip anyway)
+    text = re.sub(r'//[^\n]*', ' ', text)
+    text = re.sub(r'^[ \t]*#[^\n]*$', ' ', text, flags=re.M)         # preprocessor lines (none is continued)
+    protos = {}
+    for ret, name, params in re.findall(r'([A-Za-z_][\w\s*]*?)\b(pk_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', text):
+        assert name not in protos, f'{name} declared twice'
+        args = []
+        if params.strip() != 'void':
+            for i, decl in enumerate(params.split(',')):
+                tokens = re.findall(r'\w+|\*', decl)
+                # every parameter of the header is named: the name is what follows the last `*`, or the last word
+                n_type = len(tokens) - tokens[::-1].index('*') if '*' in tokens else len(tokens) - 1
+                assert 0 < n_type < len(tokens) or '*' in tokens, f'{name}: cannot read parameter {i} `{decl.strip()}`'
+                args.append(ctype(tokens[:n_type], f'{name} parameter {i}'))
+        protos[name] = (ctype(re.findall(r'\w+|\*', ret), f'{name} return'), args)
+    return protos
+
+
+def _signature_mismatches(protos, table):
+    return sorted(n for n in set(protos) | set(table) if n not in protos or n not in table or
+                  (table[n][0], list(table[n][1])) != protos[n])
+
+
+def test_ctypes_signatures_have_the_types_of_the_header():
+    """lib.SIGNATURES is typed by hand: every row's return type and argument list must be what include/pasero_hip.h declares
+    (a `long long` bound as c_int truncates silently).  No function is left out, and the comparison is shown to fail on a
+    row with one LL turned into I and on a row with one argument dropped."""
+    from pasero_amd import lib
+    protos = _header_prototypes()
+    header = open(os.path.join(ROOT, 'include', 'pasero_hip.h')).read()
+    assert set(protos) == set(re.findall(r'\b(pk_[a-z0-9_]+)\s*\(', header)), 'the parser missed a declaration'
+    assert set(protos) == set(lib.SIGNATURES) and len(protos) >= 101
+    assert _signature_mismatches(protos, lib.SIGNATURES) == []
+    res, args = lib.SIGNATURES['pk_gemm']
+    narrowed = list(args)
+    narrowed[narrowed.index(lib.LL)] = lib.I
+    assert _signature_mismatches(protos, {**lib.SIGNATURES, 'pk_gemm': (res, narrowed)}) == ['pk_gemm']
+    assert _signature_mismatches(protos, {**lib.SIGNATURES, 'pk_gemm': (res, list(args)[:-1])}) == ['pk_gemm']
+
+
 @pytest.mark.parametrize('name', ['tiny_encdec_post', 'tiny_encdec_pre', 'tiny_encdec_rotary', 'tiny_encdec_swiglu', 'speech_whisper',
                                   'speech_iwslt', 'base_c1', 'tiny_adapter', 'tiny_lora', 'tiny_hd128', 'tiny_encdec_rms', 'tiny_opts_a', 'tiny_opts_b', 'tiny_hd128_rotary', 'tiny_lora_rotary', 'tiny_freeze_embed', 'tiny_freeze_shared'])
 def test_parameter_names_and_shapes_match_reference(name):
